@@ -14,6 +14,11 @@ collective; documents shard with no data-path exchange, so scaling is weak: each
 templates).  Failure records are written to HBM each step, in place, where the device reporter reads
 them.
 
+A plain run (`--gpus 1 --steps N --warmup W`) loads the corpus, warms up, times the N steps, writes the
+last step's outputs when --dump-outputs DIR is given (dump_outputs) and prints the line: metric, value,
+ms_per_step, roofline and detail.  --full adds cpu_baseline, the e2e figures and, for N > 1, the report
+gather described below; the line is then the same with those keys filled.
+
 roofline: HBM-bound.  Algorithmic bytes per launch = arena bytes (nodes x 16 B + string pool +
 roots, each template counted once however many rules files read it) + per-tile outputs
 (32 B TileOut + 1 B per top-level rule) + record bytes (48 B each).  `achieved` divides that
@@ -220,6 +225,42 @@ def load_pmc(workload):
     return None
 
 
+DUMP_MAX_TILES = 8 << 20     # --dump-outputs writes the status of up to this many tiles whole (float32: 32 MB)
+DUMP_SAMPLE_TILES = 2 << 20  # ... and of more, a sample of this many (float32 statuses + float64 indices: 24 MB)
+DUMP_REPORT_DOCS = 16        # documents whose structured report --dump-outputs writes
+DUMP_REPORT_BYTES = 4 << 20  # ... and at most this many of its bytes (float32: 16 MB)
+
+
+def dump_outputs(path, sess, counts, ntiles, ndocs, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step (launch, tally
+    all-reduce, fetch), as <name>.npy files of float32 / float64, at most 64 MB in all:
+
+    rule_tallies   the per-rule PASS / FAIL / SKIP tallies, all-reduced over the ranks (the bound tensor)
+    tile_counts    the rank's tiles by status: FAIL, PASS, SKIP, error
+    tile_status    the status of every (document, rules file) tile in tile order (guard_types.h ST_*); of more
+                   than DUMP_MAX_TILES tiles a fixed sample of DUMP_SAMPLE_TILES (numpy default_rng(0),
+                   ascending), whose tile numbers are in tile_index
+    report_sample  the bytes of the structured JSON report of the first DUMP_REPORT_DOCS documents, rendered
+                   from the last step's failure records (at most DUMP_REPORT_BYTES of them)
+    """
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+    save("rule_tallies", counts.detach().cpu().numpy().astype(np.float64))
+    save("tile_counts", np.array([sess.stat(4), sess.stat(5), sess.stat(6), sess.stat(7)], dtype=np.float64))
+    status = np.frombuffer(sess.tile_status(ntiles), dtype=np.uint8)
+    if ntiles > DUMP_MAX_TILES:
+        index = np.sort(np.random.default_rng(0).choice(ntiles, DUMP_SAMPLE_TILES, replace=False))
+        status = status[index]
+        save("tile_index", index.astype(np.float64))   # exact: tile numbers are far below 2^53
+    save("tile_status", status.astype(np.float32))
+    raw, _ = sess.report_range_raw("json", 0, min(ndocs, DUMP_REPORT_DOCS))
+    save("report_sample", np.asarray(raw[:DUMP_REPORT_BYTES]).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -267,7 +308,20 @@ def main():
     ap.add_argument("--cpu-per-core", type=int, default=0)
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL); gloo only to rehearse N ranks sharing one GPU (GG_BENCH_DEVICE)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline with its full-size parity "
+                         "check, the e2e phases and streamed legs, and for N > 1 the report gather (--no-cpu-baseline, "
+                         "--no-e2e and --gather-docs 0 switch them off one by one); without it the run loads, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.no_e2e = True
+        args.gather_docs = 0
     if not args.docs:
         args.docs = {"cfg5": 303_031, "cfg4": 8192}.get(args.workload, 1_000_000)
     if not args.cpu_per_core:
@@ -458,6 +512,9 @@ def main():
         cpu.pop("_reports", None)
     tally_sum = int(counts.sum().item())   # the all-reduced tensor: every rank's last-step tallies
     n_fail, n_pass, n_skip, n_err = sess.stat(4), sess.stat(5), sess.stat(6), sess.stat(7)
+    if args.dump_outputs:
+        log("dump outputs to %s" % args.dump_outputs)
+        dump_outputs(args.dump_outputs, sess, counts, ntiles, ndocs, suffix=".rank%d" % rank if world > 1 else "")
 
     gather = None
     if world > 1 and args.gather_docs != 0:

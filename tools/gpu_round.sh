@@ -3,7 +3,7 @@
 # step ends the session (no GPU work after a failure).  Steps:
 #   tests          python -m pytest tests -m gpu ($PYTEST_K selects)
 #   smoke          __graft_entry__.smoke()
-#   bench:<cfg>    bench.py --workload <cfg> $BENCH_ARGS (the full line: cpu_baseline, e2e)
+#   bench:<cfg>    bench.py --full --workload <cfg> $BENCH_ARGS (the full line: cpu_baseline, e2e)
 #   ktrace:<cfg>   rocprofv3 --kernel-trace --stats of bench.py --workload <cfg> (5 timed steps)
 #   pmc:<cfg>      FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.sh)
 #   lds:<cfg>      SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE / SQ_INSTS_LDS pass
@@ -27,7 +27,7 @@ for step in $STEPS; do
       (cd $R && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1) || { tail -20 $O/smoke.log; exit 1; }
       tail -1 $O/smoke.log;;
     bench:*)
-      (cd $R && timeout -k 10 900 python3 -u bench.py --workload $W $BENCH_ARGS > $O/bench_$W.json 2> $O/bench_$W.log) || { tail -10 $O/bench_$W.log; exit 1; }
+      (cd $R && timeout -k 10 900 python3 -u bench.py --full --workload $W $BENCH_ARGS > $O/bench_$W.json 2> $O/bench_$W.log) || { tail -10 $O/bench_$W.log; exit 1; }
       cut -c1-2500 $O/bench_$W.json;;
     ktrace:*)
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktrace_$W -o run -- \
