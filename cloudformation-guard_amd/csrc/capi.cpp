@@ -33,6 +33,7 @@
 #include "host_format.h"
 #include "json_gpu.h"
 #include "eisel_lemire.h"
+#include "yaml_scalar.h"
 #include "program.h"
 #include "report_gpu.h"
 #include "reporter.h"
@@ -55,6 +56,7 @@ __global__ void root_resources_kernel(const DNode* nodes, const uint64_t* base, 
 __global__ void pack_nodes_kernel(const DNode* in, DNodeP* out, uint32_t* klen, uint32_t* parent, uint64_t n, uint32_t* bad);
 __global__ void report_kernel(RenderArgs A, uint32_t write);
 __global__ void report_sarif_kernel(RenderArgs A, uint32_t write);
+__global__ void report_yaml_kernel(RenderArgs A, uint32_t write);
 void d2h_push(void* dst, const void* src, size_t bytes, hipStream_t st, int blocks);
 __global__ void rec_block_sums_kernel(const TileOut* tiles, uint32_t n, uint32_t* bsum);
 __global__ void rec_scan_sums_kernel(uint32_t* bsum, uint32_t nb, uint32_t* total);
@@ -1274,8 +1276,11 @@ void render_tables(gg_session* s) {
 // documents between them -- while the device renders the next block.
 // the streamed entries' shader copy-out (device_report_text push_default): workgroups of d2h_push
 static constexpr int kStreamPushBlocks = 32;
+// OUT_YAML: every document is one item of the root sequence ("- name: ..." to its last "\n"; the parts
+// concatenate); *yaml_open is set when a host-written document leaves libyaml's stream open-ended (a
+// "|+" scalar): the report then ends in "...\n", which the caller appends.
 bool device_report_text(gg_session* s, size_t first, size_t count, size_t report_first, ReportSink& sink, ReportError& err,
-                        DevReportStats* stats, int32_t fmt, int push_default = 0) {
+                        DevReportStats* stats, int32_t fmt, int push_default = 0, bool* yaml_open = nullptr) {
   bind_device(s);
   render_tables(s);
   hipStream_t st = s->dv->stream;
@@ -1379,6 +1384,16 @@ bool device_report_text(gg_session* s, size_t first, size_t count, size_t report
             if (fmt == OUT_SARIF) {
               std::string t;
               if (!sarif_doc_results(s->docs, (uint32_t)d, progs, tp, t, cerr)) { failed = true; break; }
+              sink.write(t.data(), t.size());
+              S.bytes += t.size();
+            } else if (fmt == OUT_YAML) {
+              ReportWriter w(OUT_YAML);   // the host YamlOut: a one-item root sequence
+              if (!w.add(s->docs, (uint32_t)d, progs, tp, cerr)) { failed = true; break; }
+              std::string t = w.finish();
+              if (t.size() >= 5 && t.compare(t.size() - 5, 5, "\n...\n") == 0) {
+                t.resize(t.size() - 4);
+                if (yaml_open) *yaml_open = true;
+              }
               sink.write(t.data(), t.size());
               S.bytes += t.size();
             } else {
@@ -1494,7 +1509,7 @@ bool device_report_text(gg_session* s, size_t first, size_t count, size_t report
     A.names = R.names.p; A.name_off = R.name_off.p; A.sizes = R.sizes.p;
     const uint32_t blocks = (uint32_t)std::min<size_t>((nb + 255) / 256, (size_t)dev_ncu(s->device) * 8);
     HIPCHK(hipEventRecord(e0, st));
-    auto kern = fmt == OUT_SARIF ? report_sarif_kernel : report_kernel;
+    auto kern = fmt == OUT_SARIF ? report_sarif_kernel : fmt == OUT_YAML ? report_yaml_kernel : report_kernel;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, A, 0u);
     HIPCHK(hipGetLastError());
     b.sizes.resize(nb);
@@ -1643,6 +1658,27 @@ bool shards_report(const std::vector<ShardView>& sh, std::string& out, int32_t& 
     }
     if (results.n) sink.write("\n      ", 7);
     sink.write(tail.data(), tail.size());
+    *cstr = sink.take();
+    if (anyfail) exit_code = 19;
+    return true;
+  }
+  bool yaml_dev = fmt == OUT_YAML && cstr && !sh.empty();   // (the streamed entries pass no cstr: host writer)
+  for (const ShardView& v : sh) yaml_dev = yaml_dev && (v.count == 0 || (device_report_on(v.s) && v.s->fetched_on_device));
+  if (yaml_dev) {
+    // the FileReports rendered on the shards' devices as items of one root sequence (report_yaml_kernel),
+    // concatenated in document order; the host arena is fetched only if a document falls back
+    BufferSink sink;
+    size_t ndocs = 0;
+    bool open_ended = false;
+    for (const ShardView& v : sh) {
+      if (!v.count) continue;
+      if (!device_report_text(v.s, v.first, v.count, SIZE_MAX, sink, err, nullptr, OUT_YAML, 0, &open_ended)) { exit_code = -1; return false; }
+      ndocs += v.count;
+      const size_t nf = v.s->progs.size();
+      for (size_t t = v.first * nf; t < (v.first + v.count) * nf; t++) if (v.s->tiles[t].status == ST_FAIL) anyfail = true;
+    }
+    if (!ndocs) sink.write("[]\n", 3);
+    if (open_ended) sink.write("...\n", 4);
     *cstr = sink.take();
     if (anyfail) exit_code = 19;
     return true;
@@ -3734,6 +3770,47 @@ int64_t gg_session_report_sarif_device(gg_session* s, size_t max_docs, int32_t* 
   } catch (std::exception& e) { set_err(err, -1, e.what()); return -1; }
 }
 
+// The YAML report of the first max_docs documents (0: all) rendered on the device (report_yaml_kernel), copied
+// to host memory and dropped (measurement, as gg_session_report_json_device; the same eight stats).
+int64_t gg_session_report_yaml_device(gg_session* s, size_t max_docs, int32_t* exit_code, double* stats, extern_err_t* err) {
+  set_err(err, 0, "");
+  if (!s->evaluated || !s->fetched_on_device) { set_err(err, -1, "session not evaluated and fetched on a device"); return -1; }
+  try {
+    std::vector<const Program*> progs;
+    for (auto& p : s->progs) progs.push_back(&p->prog);
+    const size_t nf = progs.size(), nd = max_docs ? std::min(max_docs, s->docs.ndocs()) : s->docs.ndocs();
+    for (size_t t = 0; t < nd * nf; t++)
+      if (s->tiles[t].err) {
+        ensure_host_arena(s);
+        ReportError re;
+        tile_error(s->docs, (uint32_t)(t / nf), *progs[t % nf], s->tiles[t], re);
+        set_err(err, ffi_code(re.kind), error_display(re.kind, re.msg));
+        if (exit_code) *exit_code = -1;
+        return -1;
+      }
+    bind_device(s);
+    render_tables(s);
+    CountingSink sink(s->dv->pinned, DeviceBufs::kPinnedBytes);
+    DevReportStats st;
+    ReportError re;
+    bool open_ended = false;
+    if (!device_report_text(s, 0, nd, SIZE_MAX, sink, re, &st, OUT_YAML, 0, &open_ended)) {
+      set_err(err, ffi_code(re.kind), error_display(re.kind, re.msg));
+      if (exit_code) *exit_code = -1;
+      return -1;
+    }
+    const int64_t bytes = (int64_t)sink.n + (nd ? 0 : 3) + (open_ended ? 4 : 0);   // "[]\n" when empty, "...\n"
+    bool anyfail = false;
+    for (size_t t = 0; t < nd * nf; t++) if (s->tiles[t].status == ST_FAIL) anyfail = true;
+    if (exit_code) *exit_code = anyfail ? 19 : (s->parse_errors.empty() ? 0 : 5);
+    if (stats) {
+      stats[0] = (double)st.device_docs; stats[1] = (double)st.host_docs; stats[2] = st.size_ms; stats[3] = st.write_ms;
+      stats[4] = st.d2h_ms; stats[5] = st.host_ms; stats[6] = (double)st.bytes; stats[7] = 0;
+    }
+    return bytes;
+  } catch (std::exception& e) { set_err(err, -1, e.what()); return -1; }
+}
+
 // a native write callback for cfn_guard_validate_batch_stream(_devices) that counts the bytes into *(uint64_t*)ctx
 // and drops them (measurement: the report reaches host memory with no consumer cost on the path)
 int32_t gg_count_write(void* ctx, const char*, size_t len) {
@@ -3889,6 +3966,18 @@ int32_t gg_parse_f64(const char* s, size_t n, double* out) {
     return 0;
   memcpy(out, &bits, 8);
   return 1;
+}
+
+// the device YAML writer's scalar machine (yaml_scalar.h) on the host: `text` as it follows "k:" in a mapping
+// whose keys sit at column `indent` (the separating space, the scalar, no final break), or as that mapping's
+// key.  Returns the length written to out[0..cap), -1 when the device writer hands the document to the host
+// writer (or cap is too small).
+int64_t gg_yaml_scalar(const char* text, size_t len, uint32_t indent, int32_t is_key, char* out, size_t cap) {
+  struct { std::string s; void put(char c) { s.push_back(c); } } o;
+  if (!is_key) o.put(' ');
+  if (ys::render(o, text ? text : "", (uint32_t)len, is_key != 0, indent) == ys::HOST || o.s.size() > cap) return -1;
+  memcpy(out, o.s.data(), o.s.size());
+  return (int64_t)o.s.size();
 }
 
 int32_t gg_regex_match(const char* pattern, const char* text, size_t len, uint32_t* stats) {

@@ -11,6 +11,11 @@
 // Debug-formatted reasons, map keys or count() values as values, ranges / chars, nesting past 48) is
 // flagged in the size pass and written by the host writer at its position, so the bytes never depend on
 // which writer ran.
+//
+// The YAML report (`-o yaml`) goes the same way through report_yaml_kernel (report_yaml_gpu.hip: the same
+// record walk compiled with the block-YAML writer, scalar styles by yaml_scalar.h): one item of the root
+// sequence per document, the same passes, blocks and fallback; libyaml-only cases ("|+" literals, complex
+// keys) join the fallback list.
 #pragma once
 #include <stdint.h>
 

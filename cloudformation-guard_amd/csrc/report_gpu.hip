@@ -8,6 +8,9 @@
 
 #include "report_gpu.h"
 
+#define GG_HD __host__ __device__ __attribute__((always_inline))
+#include "yaml_scalar.h"
+
 namespace gg {
 namespace rg {
 
@@ -18,7 +21,7 @@ static const uint32_t KEY_BIT = 0x20000000u;
 static const uint32_t kMaxDepth = 48;   // JSON nesting a document may reach on the device (else the host writes it)
 
 // fallback reasons (W.fb): why the host writer takes a document
-enum : uint32_t { FB_NONE = 0, FB_FLOAT = 1, FB_DEBUG = 2, FB_REF = 3, FB_KIND = 4, FB_DEPTH = 5 };
+enum : uint32_t { FB_NONE = 0, FB_FLOAT = 1, FB_DEBUG = 2, FB_REF = 3, FB_KIND = 4, FB_DEPTH = 5, FB_YAML = 6 };
 
 // ---------------------------------------------------------------------------------- writer ---
 // p == null: the size pass (only counts).  JW state: `depth` open containers, bit i of `first`: container
@@ -36,7 +39,13 @@ struct W {
 // (every writer function is inlined into the kernels: a W passed to a real call would live in scratch and
 // every byte would become scratch traffic; the byte-level functions stay trivial so the inlined kernels
 // compile in reasonable time)
+#ifdef GG_REPORT_YAML
+// (the YAML unit: the walk's larger functions are real calls -- each compiled once.  Inlined like the JSON
+// writer's, the one kernel compiles for 17 to 30 minutes; the byte-level functions stay inline)
+#define RN __device__ __attribute__((noinline))
+#else
 #define RN RD
+#endif
 RD void raw(W& w, char c) {
   if (w.p) w.p[w.n] = c;
   w.n++;
@@ -101,26 +110,30 @@ RD void tput(W& w, char c) {
   }
   emit(w, c);
 }
-RN void tlit(W& w, const char* s) { for (; *s; s++) tput(w, *s); }
+template <class WT> RN void tlit(WT& w, const char* s) { for (; *s; s++) tput(w, *s); }
 RD void tstr(W& w, const char* s, uint32_t n) {
   if (!w.dotf) { bulk(w, s, n, w.esc); return; }
   for (uint32_t i = 0; i < n; i++) tput(w, s[i]);
 }
-RN void tu64(W& w, uint64_t v) {
+template <class WT> RN void tu64(WT& w, uint64_t v) {
   char b[24];
   int k = 0;
   do { b[k++] = (char)('0' + v % 10); v /= 10; } while (v);
   while (k) tput(w, b[--k]);
 }
-RD void ti64(W& w, int64_t v) {
+template <class WT> RD void ti64(WT& w, int64_t v) {
   if (v < 0) { tput(w, '-'); tu64(w, (uint64_t)0 - (uint64_t)v); } else tu64(w, (uint64_t)v);
 }
-RD void sbeg(W& w) { raw(w, '"'); w.esc = true; }
-RD void send(W& w) {
+// a composed string: COMPOSE(w) { producer } runs the producer between sbeg and send, once for JSON; the
+// YAML writer runs it twice, analyse then emit (one loop, so the inlined producer is instantiated once)
+#define COMPOSE(w) for (uint32_t again_ = sbeg(w); again_; again_ = send(w))
+RD uint32_t sbeg(W& w) { raw(w, '"'); w.esc = true; return 1; }
+RD uint32_t send(W& w) {
   if (w.held) { w.held = false; emit(w, '.'); }
   w.dotf = false;
   w.esc = false;
   raw(w, '"');
+  return 0;
 }
 RD void jstr(W& w, const char* s, uint32_t n) { raw(w, '"'); bulk(w, s, n, true); raw(w, '"'); }
 RN void jlit(W& w, const char* s) { raw(w, '"'); for (; *s; s++) esc1(w, (unsigned char)*s); raw(w, '"'); }
@@ -146,15 +159,182 @@ RD void item(W& w) {
   spaces(w, 2 * (w.base + L + 1));
 }
 RD void key(W& w, const char* k) { item(w); raw(w, '"'); raws(w, k); raw(w, '"'); raw(w, ':'); raw(w, ' '); }
+RD void kstr(W& w, const char* s, uint32_t n) { item(w); jstr(w, s, n); raw(w, ':'); raw(w, ' '); }   // a document's map key
 RD void jnull(W& w) { raws(w, "null"); }
+RD void jbool(W& w, bool b) { raws(w, b ? "true" : "false"); }
+RD void jint(W& w, int64_t v) { const bool e = w.esc; w.esc = false; ti64(w, v); w.esc = e; }
+// a document's FileReport begins: ",\n" after the report's first, the root array's indent
+RD void doc_begin(W& w, bool first) {
+  if (!first) { raw(w, ','); raw(w, '\n'); }
+  spaces(w, 2);
+  w.depth = 0; w.base = 1; w.first = 0; w.esc = false; w.dotf = false; w.held = false;
+}
+RD void doc_end(W&) {}
 __device__ const char* const kCmp[] = {"Eq", "In", "Gt", "Lt", "Le", "Ge", "Exists", "Empty", "IsString", "IsList", "IsMap",
                                       "IsBool", "IsInt", "IsFloat", "IsNull"};
-RN void cmp(W& w, uint32_t op, bool neg) {
+template <class WT> RN void cmp(WT& w, uint32_t op, bool neg) {
   open(w, '[');
-  item(w); raw(w, '"'); raws(w, op < 15 ? kCmp[op] : "Eq"); raw(w, '"');
-  item(w); raws(w, neg ? "true" : "false");
+  item(w); jlit(w, op < 15 ? kCmp[op] : "Eq");
+  item(w); jbool(w, neg);
   close(w, ']');
 }
+
+// ----------------------------------------------------------------------------- YAML writer ---
+// The same walk writes block YAML through Y: serde_yaml 0.9 over libyaml 0.2.5, width unlimited (reporter.cpp
+// YamlOut).  A scalar's style depends on the whole string, so every string runs through yaml_scalar.h twice:
+// scanned, then emitted in the style decided (COMPOSE runs a composed string's producer once per phase).
+// Layout: level i of the open collections is a sequence when bit i of `seq` is set and still has no entry
+// when bit i of `empty` is set (its open is deferred to the first entry: an empty one is " []" / " {}" on
+// its key's line).  Entries of a mapping under a mapping go two columns in, a sequence under a mapping key
+// is indentless, a collection inside a sequence entry is compact ("- k: v", "- - x"), so the column of
+// level i follows from the masks alone.  Every line is preceded by its break; doc_end writes the last one.
+struct Y {
+  char* p;
+  uint64_t n;
+  uint32_t fb;
+  uint32_t depth;
+  uint64_t seq, empty;
+  bool dotf, held, dash, emitting;   // dash: the entry in progress follows "-" (else "key:")
+  ys::Sc sc;
+  __device__ void put(char c) { if (p) p[n] = c; n++; }
+};
+RD void raw(Y& y, char c) { y.put(c); }
+RD void raws(Y& y, const char* s) { for (; *s; s++) y.put(*s); }
+RD void spaces(Y& y, uint32_t k) {
+  if (y.p) for (uint32_t i = 0; i < k; i++) y.p[y.n + i] = ' ';
+  y.n += k;
+}
+// the column of level L's entries: the document's mapping (level 0) sits at 2, after the root sequence's "- "
+RD uint32_t col(const Y& y, uint32_t L) {
+  const uint64_t indentless = y.seq & ~(y.seq << 1) & ~1ull & ((2ull << L) - 1);
+  return 2u + 2u * L - 2u * (uint32_t)__popcll(indentless);
+}
+RD void open(Y& y, char c) {
+  if (y.depth >= 63) { y.fb = FB_DEPTH; return; }
+  const uint64_t b = 1ull << y.depth;
+  y.seq = c == '[' ? (y.seq | b) : (y.seq & ~b);
+  y.empty |= b;
+  y.depth++;
+}
+RD void close(Y& y, char c) {
+  if (y.depth == 0) { y.fb = FB_DEPTH; return; }
+  y.depth--;
+  if ((y.empty >> y.depth) & 1ull) { raw(y, ' '); raw(y, c == ']' ? '[' : '{'); raw(y, c); }
+}
+// the next entry of the innermost collection starts: its line, or -- the first entry of a collection that
+// is itself a sequence entry -- the rest of the "-" line
+RD void entry(Y& y) {
+  if (y.depth == 0) { y.fb = FB_DEPTH; return; }
+  const uint32_t L = y.depth - 1;
+  const bool first = (y.empty >> L) & 1ull;
+  y.empty &= ~(1ull << L);
+  if (first && y.dash) { raw(y, ' '); return; }
+  raw(y, '\n'); spaces(y, col(y, L));
+}
+RD void item(Y& y) { entry(y); raw(y, '-'); y.dash = true; }
+RD void key(Y& y, const char* k) { entry(y); raws(y, k); raw(y, ':'); y.dash = false; }   // the report's own keys: plain
+// The scalar machine's common bytes are handled inline (scan_fast / emit_fast: a few compares); the rest --
+// first characters, indicators, breaks, UTF-8, double-quoted escapes -- are real calls that take and return
+// the machine's state by value and never the writer, whose text pointer and count stay in registers.
+struct DqOut { uint32_t cp, need, lo, n; uint32_t w[3]; __device__ void put(char c) { w[n >> 2] |= (uint32_t)(unsigned char)c << (8 * (n & 3)); n++; } };
+__device__ __attribute__((noinline)) ys::Sc scan_call(ys::Sc s, uint32_t b) { ys::scan_slow(s, (unsigned char)b); return s; }
+__device__ __attribute__((noinline)) DqOut dq_call(uint32_t cp, uint32_t need, uint32_t lo, uint32_t b) {
+  ys::Sc s{};
+  s.cp = cp; s.need = need; s.lo = lo;
+  DqOut o{};   // one character's escape is at most 10 bytes ("\\UXXXXXXXX")
+  ys::emit_slow(s, o, (unsigned char)b);
+  o.cp = s.cp; o.need = s.need; o.lo = s.lo;
+  return o;
+}
+RD void feed(Y& y, char c) {
+  if (!y.emitting) {
+    if (!ys::scan_fast(y.sc, (unsigned char)c)) y.sc = scan_call(y.sc, (unsigned char)c);
+    return;
+  }
+  if (ys::emit_fast(y.sc, y, (unsigned char)c)) return;
+  const DqOut o = dq_call(y.sc.cp, y.sc.need, y.sc.lo, (unsigned char)c);
+  y.sc.cp = o.cp; y.sc.need = o.need; y.sc.lo = o.lo;
+  for (uint32_t i = 0; i < o.n; i++) raw(y, (char)(o.w[i >> 2] >> (8 * (i & 3))));
+}
+RD void emit(Y& y, char c) { feed(y, c); }
+RD void tput(Y& y, char c) {
+  if (y.dotf) {
+    if (y.held) { y.held = false; if (c != '[') feed(y, '.'); }
+    if (c == '.') { y.held = true; return; }
+  }
+  feed(y, c);
+}
+// n bytes at s through the current phase; a 16-byte aligned source (the pool) is read 16 bytes at a time,
+// chunks of plain-safe ASCII skip the scan and plain text is copied as it is
+RD void ybulk(Y& y, const char* s, uint32_t n) {
+  uint32_t i = 0;
+  if ((((uintptr_t)s) & 15u) == 0) {
+    for (; i < n; i += 16) {
+      const uint4 q = *(const uint4*)(s + i);
+      const uint64_t lo = (uint64_t)q.x | ((uint64_t)q.y << 32), hi = (uint64_t)q.z | ((uint64_t)q.w << 32);
+      const uint32_t m = n - i < 16 ? n - i : 16;
+      if (!y.emitting && m == 16 && ys::scan16(y.sc, lo, hi)) continue;
+      const bool copy = y.emitting && y.sc.style == ys::PLAIN;
+#pragma unroll 1
+      for (uint32_t k = 0; k < m; k++) {
+        const char c = (char)((k < 8 ? lo >> (8 * k) : hi >> (8 * (k - 8))) & 0xFF);
+        if (copy) raw(y, c); else feed(y, c);
+      }
+    }
+    return;
+  }
+#pragma unroll 1
+  for (; i < n; i++) feed(y, s[i]);
+}
+RD void tstr(Y& y, const char* s, uint32_t n) {
+  if (!y.dotf) { ybulk(y, s, n); return; }
+  for (uint32_t i = 0; i < n; i++) tput(y, s[i]);
+}
+// the scan is over: the style, the separating space and the opening; false: libyaml writes this document
+__device__ __attribute__((noinline)) ys::Sc decide_call(ys::Sc s, bool is_key, uint32_t indent) { ys::decide(s, is_key, indent); return s; }
+RD bool decided(Y& y, bool is_key) {
+  y.sc = decide_call(y.sc, is_key, y.depth ? col(y, y.depth - 1) : 0u);
+  if (y.sc.style == ys::HOST) { y.fb = FB_YAML; return false; }
+  if (!is_key) raw(y, ' ');
+  ys::emit_open(y.sc, y);
+  y.emitting = true;
+  return true;
+}
+RD uint32_t sbeg(Y& y) { ys::begin(y.sc); y.emitting = false; return 1; }
+RD uint32_t send(Y& y) {
+  if (y.held) { y.held = false; feed(y, '.'); }
+  y.dotf = false;
+  if (y.fb) { y.emitting = false; return 0; }
+  if (!y.emitting) return decided(y, false) ? 1 : 0;
+  ys::emit_close(y.sc, y);
+  y.emitting = false;
+  return 0;
+}
+RD void yscalar(Y& y, const char* s, uint32_t n, bool is_key) {
+#pragma unroll 1
+  for (uint32_t more = sbeg(y); more;) {
+    ybulk(y, s, n);
+    if (y.emitting) { ys::emit_close(y.sc, y); y.emitting = false; more = 0; }
+    else more = decided(y, is_key) ? 1 : 0;
+  }
+}
+RD void jstr(Y& y, const char* s, uint32_t n) { yscalar(y, s, n, false); }
+RD void jlit(Y& y, const char* s) { uint32_t n = 0; while (s[n]) n++; yscalar(y, s, n, false); }
+RD void kstr(Y& y, const char* s, uint32_t n) { entry(y); yscalar(y, s, n, true); raw(y, ':'); y.dash = false; }
+RD void jnull(Y& y) { raws(y, " null"); }
+RD void jbool(Y& y, bool b) { raws(y, b ? " true" : " false"); }
+RD void jint(Y& y, int64_t v) {   // serde_yaml writes integers plain
+  raw(y, ' ');
+  y.emitting = true; y.sc.style = ys::PLAIN;
+  ti64(y, v);
+  y.emitting = false;
+}
+// a document's FileReport is one entry of the root sequence: "-" at column 0, its mapping compact
+RD void doc_begin(Y& y, bool) {
+  y.depth = 0; y.seq = 0; y.empty = 0; y.dotf = false; y.held = false; y.emitting = false;
+  raw(y, '-'); y.dash = true;
+}
+RD void doc_end(Y& y) { raw(y, '\n'); }
 
 // ---------------------------------------------------------------------------------- values ---
 struct Ctx {
@@ -205,7 +385,7 @@ RD const char* type_info(uint32_t k) {
 }
 
 // JSON pointer of `ref` (DocBatch::path): the ancestors' keys / indices, root first
-RN void path(W& w, const Ctx& c, uint32_t ref) {
+template <class WT> RN void path(WT& w, const Ctx& c, uint32_t ref) {
   uint32_t chain[64];
   uint32_t n = 0;
   NV v;
@@ -226,14 +406,14 @@ RN void path(W& w, const Ctx& c, uint32_t ref) {
     else tu64(w, (chain[i] & ~LIT_BIT) - p.a);
   }
 }
-RD void loc(W& w, uint32_t l, uint32_t col) { tlit(w, "[L:"); tu64(w, l); tlit(w, ",C:"); tu64(w, col); tput(w, ']'); }
-RN void path_display(W& w, const Ctx& c, uint32_t ref) {
+template <class WT> RD void loc(WT& w, uint32_t l, uint32_t col) { tlit(w, "[L:"); tu64(w, l); tlit(w, ",C:"); tu64(w, col); tput(w, ']'); }
+template <class WT> RN void path_display(WT& w, const Ctx& c, uint32_t ref) {
   path(w, c, ref);
   if (!w.fb) loc(w, line_of(c, ref), col_of(c, ref));
 }
 
 // serde of a value (R::value_json / write_value): pretty JSON through the JW state
-RN void write_value(W& w, const Ctx& c, uint32_t ref) {
+template <class WT> RN void write_value(WT& w, const Ctx& c, uint32_t ref) {
   uint32_t sref[kMaxDepth], sj[kMaxDepth];
   uint32_t sp = 0;
   uint32_t cur = ref;
@@ -245,9 +425,9 @@ RN void write_value(W& w, const Ctx& c, uint32_t ref) {
     switch (n.kind) {
       case K_NULL: jnull(w); break;
       case K_STRING: jstr(w, bytes_of(c, cur) + n.a, n.count); break;
-      case K_REGEX: raw(w, '"'); esc1(w, '/'); for (uint32_t i = 0; i < n.count; i++) esc1(w, (unsigned char)bytes_of(c, cur)[n.a + i]); esc1(w, '/'); raw(w, '"'); break;
-      case K_BOOL: raws(w, n.a ? "true" : "false"); break;
-      case K_INT: { const bool e = w.esc; w.esc = false; ti64(w, ival(n)); w.esc = e; break; }
+      case K_REGEX: COMPOSE(w) { tput(w, '/'); tstr(w, bytes_of(c, cur) + n.a, n.count); tput(w, '/'); } break;
+      case K_BOOL: jbool(w, n.a != 0); break;
+      case K_INT: jint(w, ival(n)); break;
       case K_LIST:
       case K_MAP:
         if (sp == kMaxDepth) { w.fb = FB_DEPTH; return; }
@@ -267,12 +447,12 @@ RN void write_value(W& w, const Ctx& c, uint32_t ref) {
       nv(c, sref[sp - 1], m);
       if (sj[sp - 1] < m.count) {
         const uint32_t ch = child(sref[sp - 1], m, sj[sp - 1]++);
-        item(w);
         if (m.kind == K_MAP) {
           NV k;
           nv(c, ch, k);
-          jstr(w, bytes_of(c, ch) + k.key_off, k.key_len);
-          raw(w, ':'); raw(w, ' ');
+          kstr(w, bytes_of(c, ch) + k.key_off, k.key_len);
+        } else {
+          item(w);
         }
         cur = ch;
         break;
@@ -284,7 +464,7 @@ RN void write_value(W& w, const Ctx& c, uint32_t ref) {
 }
 
 // ValueOnlyDisplay (display.rs:33-107) into the current text
-RN void value_only(W& w, const Ctx& c, uint32_t ref) {
+template <class WT> RN void value_only(WT& w, const Ctx& c, uint32_t ref) {
   uint32_t sref[kMaxDepth], sj[kMaxDepth];
   uint32_t sp = 0;
   uint32_t cur = ref;
@@ -332,24 +512,24 @@ RN void value_only(W& w, const Ctx& c, uint32_t ref) {
 // ------------------------------------------------------------------------- query results ---
 RD uint32_t qkind(const QR& q) { return q.meta & 3u; }
 RD int64_t synth_val(const QR& q) { return (int64_t)(((uint64_t)q.aux << 32) | q.uref); }
-RD void q_path(W& w, const Ctx& c, const QR& q) {
+template <class WT> RD void q_path(WT& w, const Ctx& c, const QR& q) {
   if (qkind(q) == QR_SYNTH_INT && q.node == NONE) return;
   path(w, c, q.node);
 }
-RD void q_path_display(W& w, const Ctx& c, const QR& q) {
+template <class WT> RD void q_path_display(WT& w, const Ctx& c, const QR& q) {
   if (qkind(q) == QR_SYNTH_INT && q.node == NONE) { tlit(w, "[L:0,C:0]"); return; }
   path_display(w, c, q.node);
 }
-RN void pav_display(W& w, const Ctx& c, const QR& q) {
+template <class WT> RN void pav_display(WT& w, const Ctx& c, const QR& q) {
   tlit(w, "Path="); q_path_display(w, c, q);
   tlit(w, " Value=");
   if (qkind(q) == QR_SYNTH_INT) ti64(w, synth_val(q)); else value_only(w, c, q.node);
 }
-RN void unresolved_display(W& w, const Ctx& c, const QR& q) {
+template <class WT> RN void unresolved_display(WT& w, const Ctx& c, const QR& q) {
   tlit(w, "Path="); path_display(w, c, q.node);
   tlit(w, " Value="); value_only(w, c, q.node);
 }
-RN void remaining(W& w, const Ctx& c, const QR& q) {
+template <class WT> RN void remaining(WT& w, const Ctx& c, const QR& q) {
   const uint32_t qid = q.uref >> 12, step = q.uref & 0xFFFu;
   if (qid >= c.P->n_queries) { w.fb = FB_REF; return; }
   const uint32_t f = c.P->rem_first[qid], last = c.P->rem_first[qid + 1] - 1;   // entries: steps 0 .. nparts
@@ -357,7 +537,7 @@ RN void remaining(W& w, const Ctx& c, const QR& q) {
   tstr(w, c.P->text + r.off, r.len);
 }
 // the unresolved reasons the device writer covers (R::reason); Debug-formatted ones go to the host
-RN void reason(W& w, const Ctx& c, const QR& q) {
+template <class WT> RN void reason(WT& w, const Ctx& c, const QR& q) {
   const uint32_t code = (q.meta >> 8) & 0xFFu;
   const uint32_t qid = q.uref >> 12, step = q.uref & 0xFFFu;
   const uint32_t cur = q.node;
@@ -411,37 +591,37 @@ RN void reason(W& w, const Ctx& c, const QR& q) {
   }
 }
 
-RN void write_pav(W& w, const Ctx& c, const QR& q) {
+template <class WT> RN void write_pav(WT& w, const Ctx& c, const QR& q) {
   open(w, '{');
-  key(w, "path"); sbeg(w); q_path(w, c, q); send(w);
+  key(w, "path"); COMPOSE(w) { q_path(w, c, q); }
   key(w, "value");
-  if (qkind(q) == QR_SYNTH_INT) ti64(w, synth_val(q)); else write_value(w, c, q.node);
+  if (qkind(q) == QR_SYNTH_INT) jint(w, synth_val(q)); else write_value(w, c, q.node);
   close(w, '}');
 }
-RN void write_unresolved(W& w, const Ctx& c, const QR& q) {
+template <class WT> RN void write_unresolved(WT& w, const Ctx& c, const QR& q) {
   open(w, '{');
   key(w, "traversed_to");
   open(w, '{');
-  key(w, "path"); sbeg(w); path(w, c, q.node); send(w);
+  key(w, "path"); COMPOSE(w) { path(w, c, q.node); }
   key(w, "value"); write_value(w, c, q.node);
   close(w, '}');
-  key(w, "remaining_query"); sbeg(w); remaining(w, c, q); send(w);
-  key(w, "reason"); sbeg(w); reason(w, c, q); send(w);
+  key(w, "remaining_query"); COMPOSE(w) { remaining(w, c, q); }
+  key(w, "reason"); COMPOSE(w) { reason(w, c, q); }
   close(w, '}');
 }
 // table entries by index, bounds-checked (an index past the table sends the document to the host writer)
 RD uint32_t tab_n(const Ctx& c, const RStr* tab) {
   return tab == c.P->ctx ? c.P->n_ctx : tab == c.P->msgs ? c.P->n_msgs : c.P->n_rule_names;
 }
-RD void str_tab(W& w, const Ctx& c, const RStr* tab, uint32_t i) {
+template <class WT> RD void str_tab(WT& w, const Ctx& c, const RStr* tab, uint32_t i) {
   if (i >= tab_n(c, tab)) { w.fb = FB_REF; return; }
   const RStr r = tab[i]; jstr(w, c.P->text + r.off, r.len);
 }
-RD void tstr_tab(W& w, const Ctx& c, const RStr* tab, uint32_t i) {
+template <class WT> RD void tstr_tab(WT& w, const Ctx& c, const RStr* tab, uint32_t i) {
   if (i >= tab_n(c, tab)) { w.fb = FB_REF; return; }
   const RStr r = tab[i]; tstr(w, c.P->text + r.off, r.len);
 }
-RD bool clause_ok(W& w, const Ctx& c, uint32_t cid) { if (cid < c.P->n_clauses) return true; w.fb = FB_REF; return false; }
+template <class WT> RD bool clause_ok(WT& w, const Ctx& c, uint32_t cid) { if (cid < c.P->n_clauses) return true; w.fb = FB_REF; return false; }
 
 RD const char* unary_msg(uint32_t op, bool neg) {
   switch (op) {
@@ -467,10 +647,10 @@ RD const char* op_msg(uint32_t op, bool neg) {
   }
 }
 // custom message of a clause: the text, or "" (R::custom)
-RD void custom_text(W& w, const Ctx& c, const PClause& pc) { if (pc.e != NONE) tstr_tab(w, c, c.P->msgs, pc.e); }
+template <class WT> RD void custom_text(WT& w, const Ctx& c, const PClause& pc) { if (pc.e != NONE) tstr_tab(w, c, c.P->msgs, pc.e); }
 
 // NotComparable reason of a REC_CMP (R::nc_reason)
-RN void nc_reason(W& w, const Ctx& c, const Rec& rc) {
+template <class WT> RN void nc_reason(WT& w, const Ctx& c, const Rec& rc) {
   if (rc.x == NC_TYPES) {
     tlit(w, "PathAwareValues are not comparable "); tlit(w, type_info(rc.y >> 8)); tlit(w, ", "); tlit(w, type_info(rc.y & 0xFFu));
   } else if (rc.x == NC_FLOAT) {
@@ -491,7 +671,7 @@ struct RecSeq {
   uint32_t stride;
   __device__ const Rec& operator[](uint32_t i) const { return p[(size_t)i * stride]; }
 };
-RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
+template <class WT> RN void tile_items(WT& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
   uint32_t closes[kMaxDepth];
   uint32_t sp = 0;
   uint32_t i = 0;
@@ -545,10 +725,10 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         key(w, "context"); str_tab(w, c, c.P->ctx, pc.f);
         key(w, "messages"); open(w, '{');
         key(w, "custom_message"); jlit(w, "");
-        key(w, "error_message"); sbeg(w);
+        key(w, "error_message"); COMPOSE(w) {
         tlit(w, "Check was not compliant as property ["); remaining(w, c, rc.from);
         tlit(w, "] is missing. Value traversed to ["); unresolved_display(w, c, rc.from); tput(w, ']');
-        send(w);
+        }
         close(w, '}');
         key(w, "unresolved"); write_unresolved(w, c, rc.from);
         close(w, '}'); close(w, '}');
@@ -567,8 +747,8 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         close(w, '}'); close(w, '}');
         key(w, "context"); str_tab(w, c, c.P->ctx, pc.d);
         key(w, "messages"); open(w, '{');
-        key(w, "custom_message"); sbeg(w); custom_text(w, c, pc); send(w);
-        key(w, "error_message"); sbeg(w);
+        key(w, "custom_message"); COMPOSE(w) { custom_text(w, c, pc); }
+        key(w, "error_message"); COMPOSE(w) {
         if (unres) {
           tlit(w, "Check was not compliant as property ["); remaining(w, c, rc.from);
           tlit(w, "] is missing. Value traversed to ["); unresolved_display(w, c, rc.from); tlit(w, "].");
@@ -576,7 +756,7 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
           tlit(w, "Check was not compliant as property ["); q_path_display(w, c, rc.from); tlit(w, "] ");
           tlit(w, unary_msg(op, neg)); tput(w, '.');
         }
-        send(w);
+        }
         close(w, '}');
         close(w, '}'); close(w, '}'); close(w, '}');
         break;
@@ -588,15 +768,15 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         key(w, "check"); open(w, '{'); key(w, "UnResolvedContext"); str_tab(w, c, c.P->ctx, pc.d); close(w, '}');
         key(w, "context"); str_tab(w, c, c.P->ctx, pc.d);
         key(w, "messages"); open(w, '{');
-        key(w, "custom_message"); sbeg(w);
+        key(w, "custom_message"); COMPOSE(w) {
         if (pc.e != NONE && pc.e < c.P->n_msgs) {   // newlines become ';'
           const RStr r = c.P->msgs[pc.e];
           for (uint32_t k = 0; k < r.len; k++) { const char ch = c.P->text[r.off + k]; tput(w, ch == '\n' ? ';' : ch); }
         }
-        send(w);
-        key(w, "error_message"); sbeg(w);
+        }
+        key(w, "error_message"); COMPOSE(w) {
         tlit(w, "Check was not compliant as variable in context ["); tstr_tab(w, c, c.P->ctx, pc.d); tlit(w, "] was not empty");
-        send(w);
+        }
         close(w, '}');
         close(w, '}'); close(w, '}'); close(w, '}');
         break;
@@ -608,11 +788,11 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         key(w, "check"); open(w, '{'); key(w, "UnResolvedContext"); str_tab(w, c, c.P->ctx, pc.f); close(w, '}');
         key(w, "context"); str_tab(w, c, c.P->ctx, pc.d);
         key(w, "messages"); open(w, '{');
-        key(w, "custom_message"); sbeg(w); custom_text(w, c, pc); send(w);
-        key(w, "error_message"); sbeg(w);
+        key(w, "custom_message"); COMPOSE(w) { custom_text(w, c, pc); }
+        key(w, "error_message"); COMPOSE(w) {
         tlit(w, "Check was not compliant as dependent rule ["); tstr_tab(w, c, c.P->ctx, pc.f);
         tlit(w, "] did not PASS. Context ["); tstr_tab(w, c, c.P->ctx, pc.d); tput(w, ']');
-        send(w);
+        }
         close(w, '}');
         close(w, '}'); close(w, '}'); close(w, '}');
         break;
@@ -629,8 +809,8 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         item(w); open(w, '{'); key(w, "Clause"); open(w, '{'); key(w, "Binary"); open(w, '{');
         key(w, "context"); if (mk) jlit(w, ""); else str_tab(w, c, c.P->ctx, pc.d);
         key(w, "messages"); open(w, '{');
-        key(w, "custom_message"); sbeg(w); if (!mk) custom_text(w, c, pc); send(w);
-        key(w, "error_message"); sbeg(w);
+        key(w, "custom_message"); COMPOSE(w) { if (!mk) custom_text(w, c, pc); }
+        key(w, "error_message"); COMPOSE(w) {
         if (from_unres || to_unres) {
           const QR& u = from_unres ? rc.from : rc.to;
           tlit(w, "Check was not compliant as property ["); remaining(w, c, u);
@@ -641,7 +821,7 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
           tlit(w, op_msg(op, neg)); tlit(w, " value ["); pav_display(w, c, rc.to); tlit(w, "].");
         }
         if (rc.x) { tlit(w, " Error = ["); nc_reason(w, c, rc); tput(w, ']'); }
-        send(w);
+        }
         close(w, '}');
         key(w, "check"); open(w, '{');
         if (from_unres || to_unres) {
@@ -676,7 +856,7 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         key(w, "context"); if (mk) jlit(w, ""); else str_tab(w, c, c.P->ctx, pc.d);
         key(w, "messages"); open(w, '{');
         key(w, "custom_message"); if (mk || pc.e == NONE) jnull(w); else str_tab(w, c, c.P->msgs, pc.e);
-        key(w, "error_message"); sbeg(w);
+        key(w, "error_message"); COMPOSE(w) {
         tlit(w, "Check was not compliant as property ["); q_path_display(w, c, rc.from); tlit(w, "] was not present in [");
         w.dotf = true;   // the items joined by '.', then every '.' before a '[' dropped (reporter.cpp "fixed")
         for (uint32_t k = 0; k < have; k++) {
@@ -689,7 +869,7 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
         if (w.held) { w.held = false; emit(w, '.'); }
         w.dotf = false;
         tput(w, ']');
-        send(w);
+        }
         close(w, '}');
         key(w, "check"); open(w, '{'); key(w, "InResolved"); open(w, '{');
         key(w, "from"); write_pav(w, c, rc.from);
@@ -712,6 +892,7 @@ RN void tile_items(W& w, const Ctx& c, const RecSeq recs, uint32_t nrec) {
   while (sp && !w.fb) { close(w, ']'); close(w, '}'); close(w, '}'); sp--; }
 }
 
+#ifndef GG_REPORT_YAML
 // ------------------------------------------------------------------------------- SARIF ---
 // SarifResults::from (sarif.rs:127-160) for one tile: every message of every ClauseReport
 // (ClauseReport::get_message, eval_context.rs:1808-1826 -- a Rule's and a Disjunction's checks flattened,
@@ -932,13 +1113,13 @@ RN void file_sarif(W& w, const RenderArgs& A, uint32_t doc) {
   }
 }
 
+#endif  // !GG_REPORT_YAML
+
 // one document's FileReport (write_file_report), preceded by ",\n" after the report's first document and
 // the array's two-space indent
-RN void file_report(W& w, const RenderArgs& A, uint32_t doc) {
+template <class WT> RN void file_report(WT& w, const RenderArgs& A, uint32_t doc) {
   const uint32_t k = doc - A.doc0;
-  if (doc != A.report_first) { raw(w, ','); raw(w, '\n'); }
-  spaces(w, 2);
-  w.depth = 0; w.base = 1; w.first = 0; w.esc = false; w.dotf = false; w.held = false;
+  doc_begin(w, doc == A.report_first);
   const uint32_t nf = A.nfiles;
   uint32_t status = ST_SKIP;
   for (uint32_t f = 0; f < nf; f++) {
@@ -975,10 +1156,12 @@ RN void file_report(W& w, const RenderArgs& A, uint32_t doc) {
     close(w, ']');
   }
   close(w, '}');
+  doc_end(w);
 }
 
 }  // namespace rg
 
+#ifndef GG_REPORT_YAML
 // One kernel for both passes (one instantiation of the inlined writer: it is large).  Size pass (write 0):
 // the bytes of each document of the block, or kHostDoc | reason for the host writer.  Write pass (write 1):
 // each device document at offsets[k] of the block's contiguous text.  Capped at 128 VGPRs (4 waves per
@@ -1008,5 +1191,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) r
     if (!write) A.sizes[k] = w.fb ? (kHostDoc | w.fb) : w.n;
   }
 }
+#else
+// The YAML report (rg::file_report through rg::Y): one lane per document, one item of the report's root
+// sequence each, in the same two passes and launch shape; compiled as a unit of its own
+// (report_yaml_gpu.hip) so the JSON and SARIF kernels above keep their code.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) report_yaml_kernel(RenderArgs A, uint32_t write) {
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < A.ndocs; k += gridDim.x * blockDim.x) {
+    rg::Y y{};
+    if (write) {
+      if (A.sizes[k] & kHostDoc) continue;
+      y.p = A.out + A.offsets[k];
+    }
+    rg::file_report(y, A, A.doc0 + k);
+    if (!write) A.sizes[k] = y.fb ? (kHostDoc | y.fb) : y.n;
+  }
+}
+#endif
 
 }  // namespace gg

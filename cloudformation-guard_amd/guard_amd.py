@@ -101,6 +101,12 @@ def lib():
     L.gg_session_report_json_device.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ExternError)]
     L.gg_session_report_json_device.restype = ctypes.c_int64
+    if hasattr(L, "gg_session_report_yaml_device"):
+        L.gg_session_report_yaml_device.argtypes = L.gg_session_report_json_device.argtypes
+        L.gg_session_report_yaml_device.restype = ctypes.c_int64
+        L.gg_yaml_scalar.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int32, ctypes.c_char_p,
+                                     ctypes.c_size_t]
+        L.gg_yaml_scalar.restype = ctypes.c_int64
     if hasattr(L, "gg_session_report_sarif_device"):
         L.gg_session_report_sarif_device.argtypes = L.gg_session_report_json_device.argtypes
         L.gg_session_report_sarif_device.restype = ctypes.c_int64
@@ -221,6 +227,17 @@ def parse_f64(text):
     b = _b(text)
     out = ctypes.c_double(0)
     return out.value if lib().gg_parse_f64(b, len(b), ctypes.byref(out)) == 1 else None
+
+
+def yaml_scalar(text, indent=0, is_key=False):
+    """the device YAML writer's scalar machine on the host: `text` (str or bytes) as it follows "k:" in a
+    mapping whose keys sit at column `indent`, or as that mapping's key; None when the device writer leaves
+    the document to the host writer"""
+    b = text if isinstance(text, bytes) else text.encode("utf-8")
+    cap = 12 * len(b) + 64 + (indent + 3) * (b.count(b"\n") + 2)
+    out = ctypes.create_string_buffer(cap)
+    n = lib().gg_yaml_scalar(b, len(b), indent, int(is_key), out, cap)
+    return None if n < 0 else out.raw[:n]
 
 
 def regex_match(pattern, text):
@@ -665,8 +682,20 @@ class Session:
         keys = ("device_docs", "host_docs", "size_ms", "write_ms", "d2h_ms", "host_ms", "body_bytes", "artifacts")
         return n, code.value, dict(zip(keys, list(st)))
 
+    def report_yaml_device(self, max_docs=0):
+        """the YAML report of the first max_docs documents (0: all) rendered on the device, copied to host
+        memory and discarded: (bytes, exit code, stats)"""
+        code = ctypes.c_int32(0)
+        st = (ctypes.c_double * 8)()
+        err = ExternError()
+        n = lib().gg_session_report_yaml_device(self.s, max_docs, ctypes.byref(code), st, ctypes.byref(err))
+        if err.code != 0:
+            _raise(err)
+        keys = ("device_docs", "host_docs", "size_ms", "write_ms", "d2h_ms", "host_ms", "body_bytes")
+        return n, code.value, dict(zip(keys, list(st)[:7]))
+
     def set_device_report(self, on):
-        """JSON reports rendered on the device (True), on host threads (False), or per GG_DEVICE_REPORT (None)"""
+        """JSON / YAML / SARIF reports rendered on the device (True), on host threads (False), or per GG_DEVICE_REPORT (None)"""
         lib().gg_session_set_device_report(self.s, -1 if on is None else int(bool(on)))
 
     def report_shards(self, output="json", cuts=()):

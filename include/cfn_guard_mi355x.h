@@ -263,6 +263,11 @@ int64_t gg_session_report_bytes(gg_session *s, int32_t output_format, size_t max
 int64_t gg_session_report_json_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
 /* the SARIF report (artifacts + frame on the host, FAILed documents' results rendered on the device), counted */
 int64_t gg_session_report_sarif_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
+/* the YAML report (`-o yaml`: one item of the root sequence per document, rendered on the device by
+ * csrc/report_yaml_gpu.hip, byte for byte the host libyaml writer's text), counted; the same stats.  A
+ * document the device writer leaves to libyaml ("|+" scalars, complex keys, floats, ...) is written by the
+ * host writer at its position. */
+int64_t gg_session_report_yaml_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
 /* JSON reports of this session (gg_session_report*, the batch entry points): 1 rendered on the device
  * (default, GG_DEVICE_REPORT=0 turns it off), 0 on host threads, -1 back to the environment's choice. */
 int32_t gg_session_set_device_report(gg_session *s, int32_t on);
@@ -318,6 +323,11 @@ int32_t gg_session_add_synthetic_device_fmt(gg_session *s, uint64_t first, size_
 /* Host diagnostic: the device loader's float parser (Eisel-Lemire, csrc/eisel_lemire.h) on the JSON
  * number s[0..n): 1 = *out is the correctly rounded double, 0 = refused (its document loads on the host). */
 int32_t gg_parse_f64(const char *s, size_t n, double *out);
+/* Host diagnostic: the device YAML writer's scalar machine (csrc/yaml_scalar.h) on `text`, as it follows
+ * "k:" in a mapping whose keys sit at column `indent` (separating space, scalar, no final break) or, with
+ * is_key, as that mapping's key.  Returns the bytes written to out, -1 = the device writer leaves the
+ * document to the host writer. */
+int64_t gg_yaml_scalar(const char *text, size_t len, uint32_t indent, int32_t is_key, char *out, size_t cap);
 /* 1 = the device loader builds the host loader's arena (up to string ids), 0 = differs, -1 = refused */
 int32_t gg_loader_device_check(const char *const *texts, const size_t *lens, size_t n, extern_err_t *err);
 
