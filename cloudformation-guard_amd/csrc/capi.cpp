@@ -57,6 +57,7 @@ __global__ void pack_nodes_kernel(const DNode* in, DNodeP* out, uint32_t* klen, 
 __global__ void report_kernel(RenderArgs A, uint32_t write);
 __global__ void report_sarif_kernel(RenderArgs A, uint32_t write);
 __global__ void report_yaml_kernel(RenderArgs A, uint32_t write);
+__global__ void report_junit_kernel(RenderArgs A, uint32_t write);
 void d2h_push(void* dst, const void* src, size_t bytes, hipStream_t st, int blocks);
 __global__ void rec_block_sums_kernel(const TileOut* tiles, uint32_t n, uint32_t* bsum);
 __global__ void rec_scan_sums_kernel(uint32_t* bsum, uint32_t nb, uint32_t* total);
@@ -1169,7 +1170,7 @@ void render_tables(gg_session* s) {
     if (n) memcpy(blob.data() + o, p, n);
     return o;
   };
-  struct Offs { size_t text, ctx, msgs, rnames, rem_first, rem, pkey, pidx, clauses, lit, lit_bytes, lit_line, lit_col; uint32_t nc, nl, nr, nq, nx, nm; };
+  struct Offs { size_t text, ctx, msgs, rnames, rem_first, rem, pkey, pidx, clauses, lit, lit_bytes, lit_line, lit_col; uint32_t nc, nl, nr, nq, nx, nm; RStr fname; };
   std::vector<Offs> offs;
   for (auto& gp : s->progs) {
     const Program& P = gp->prog;
@@ -1192,6 +1193,7 @@ void render_tables(gg_session* s) {
     }
     rem_first.push_back((uint32_t)rem.size());
     Offs o;
+    o.fname = add(P.file_name);
     o.text = put(text.data(), text.size());
     o.ctx = put(ctx.data(), ctx.size() * sizeof(RStr));
     o.msgs = put(msgs.data(), msgs.size() * sizeof(RStr));
@@ -1239,6 +1241,7 @@ void render_tables(gg_session* s) {
     r.lit = (const DNode*)(b + o.lit); r.lit_bytes = (const char*)(b + o.lit_bytes);
     r.lit_line = (const uint32_t*)(b + o.lit_line); r.lit_col = (const uint32_t*)(b + o.lit_col);
     r.n_clauses = o.nc; r.n_lit = o.nl; r.n_rule_names = o.nr; r.n_queries = o.nq; r.n_ctx = o.nx; r.n_msgs = o.nm;
+    r.file_name = o.fname;
     rp.push_back(r);
   }
   s->dv->d_rprogs.upload(rp.data(), std::max<size_t>(rp.size(), 1), st);
@@ -1279,6 +1282,7 @@ static constexpr int kStreamPushBlocks = 32;
 // OUT_YAML: every document is one item of the root sequence ("- name: ..." to its last "\n"; the parts
 // concatenate); *yaml_open is set when a host-written document leaves libyaml's stream open-ended (a
 // "|+" scalar): the report then ends in "...\n", which the caller appends.
+// OUT_JUNIT: every document is its <testsuite> element, frame-less (report_junit_kernel).
 bool device_report_text(gg_session* s, size_t first, size_t count, size_t report_first, ReportSink& sink, ReportError& err,
                         DevReportStats* stats, int32_t fmt, int push_default = 0, bool* yaml_open = nullptr) {
   bind_device(s);
@@ -1384,6 +1388,11 @@ bool device_report_text(gg_session* s, size_t first, size_t count, size_t report
             if (fmt == OUT_SARIF) {
               std::string t;
               if (!sarif_doc_results(s->docs, (uint32_t)d, progs, tp, t, cerr)) { failed = true; break; }
+              sink.write(t.data(), t.size());
+              S.bytes += t.size();
+            } else if (fmt == OUT_JUNIT) {
+              std::string t;
+              if (!junit_doc_suite(s->docs, (uint32_t)d, progs, tp, t, cerr)) { failed = true; break; }
               sink.write(t.data(), t.size());
               S.bytes += t.size();
             } else if (fmt == OUT_YAML) {
@@ -1509,7 +1518,7 @@ bool device_report_text(gg_session* s, size_t first, size_t count, size_t report
     A.names = R.names.p; A.name_off = R.name_off.p; A.sizes = R.sizes.p;
     const uint32_t blocks = (uint32_t)std::min<size_t>((nb + 255) / 256, (size_t)dev_ncu(s->device) * 8);
     HIPCHK(hipEventRecord(e0, st));
-    auto kern = fmt == OUT_SARIF ? report_sarif_kernel : fmt == OUT_YAML ? report_yaml_kernel : report_kernel;
+    auto kern = fmt == OUT_SARIF ? report_sarif_kernel : fmt == OUT_YAML ? report_yaml_kernel : fmt == OUT_JUNIT ? report_junit_kernel : report_kernel;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, A, 0u);
     HIPCHK(hipGetLastError());
     b.sizes.resize(nb);
@@ -1554,6 +1563,13 @@ bool device_report_json(gg_session* s, size_t first, size_t count, size_t report
                         DevReportStats* stats, int push_default = 0) {
   return device_report_text(s, first, count, report_first, sink, err, stats, OUT_JSON, push_default);
 }
+
+// the JUnit report's frame around the test suites (ReportWriter::finish)
+std::string junit_head(size_t tests, size_t failures) {
+  return "<?xml version=\"1.0\" encoding=\"UTF-8\"?>\n<testsuites name=\"cfn-guard validate report\" tests=\"" + std::to_string(tests) +
+         "\" failures=\"" + std::to_string(failures) + "\" errors=\"0\" time=\"0\">\n";
+}
+const char kJunitTail[] = "</testsuites>\n";
 
 // One shard of a structured report: documents [first, first + count) of a fetched session.
 struct ShardView {
@@ -1681,6 +1697,29 @@ bool shards_report(const std::vector<ShardView>& sh, std::string& out, int32_t& 
     if (open_ended) sink.write("...\n", 4);
     *cstr = sink.take();
     if (anyfail) exit_code = 19;
+    return true;
+  }
+  bool junit_dev = fmt == OUT_JUNIT && cstr && !sh.empty();
+  for (const ShardView& v : sh) junit_dev = junit_dev && (v.count == 0 || (device_report_on(v.s) && v.s->fetched_on_device));
+  if (junit_dev) {
+    // JunitReporter (xml.rs:14-80): the totals from the fetched statuses written here, every document's
+    // <testsuite> rendered on its shard's device (report_junit_kernel) and joined in document order
+    size_t tests = 0, failures = 0;
+    for (const ShardView& v : sh) {
+      const size_t nf = v.s->progs.size();
+      tests += v.count * nf;
+      for (size_t t = v.first * nf; t < (v.first + v.count) * nf; t++) failures += v.s->tiles[t].status == ST_FAIL;
+    }
+    BufferSink sink;
+    const std::string head = junit_head(tests, failures);
+    sink.write(head.data(), head.size());
+    for (const ShardView& v : sh) {
+      if (!v.count) continue;
+      if (!device_report_text(v.s, v.first, v.count, SIZE_MAX, sink, err, nullptr, OUT_JUNIT)) { exit_code = -1; return false; }
+    }
+    sink.write(kJunitTail, sizeof(kJunitTail) - 1);
+    *cstr = sink.take();
+    if (failures && exit_code != 5) exit_code = 19;   // JunitReporter::update_exit_code keeps 5 (below)
     return true;
   }
   std::vector<TextBuf> all_parts;
@@ -2976,25 +3015,32 @@ int32_t stream_format(const std::vector<int>& devs, const validate_input_t* docs
           tests += s->docs.ndocs() * nf;
           for (size_t t = 0; t < s->docs.ndocs() * nf; t++) failures += s->tiles[t].status == ST_FAIL;
         }
-        const std::string head = "<?xml version=\"1.0\" encoding=\"UTF-8\"?>\n<testsuites name=\"cfn-guard validate report\" tests=\"" +
-                                 std::to_string(tests) + "\" failures=\"" + std::to_string(failures) + "\" errors=\"0\" time=\"0\">\n";
-        static const char kTail[] = "</testsuites>\n";
+        const std::string head = junit_head(tests, failures);
         sink.write(head.data(), head.size());
         for (auto& op : outs) {
           std::string out;
           int32_t code = 0;
           ReportError re;
-          if (!session_report(op->ses.get(), out, code, re, OUT_JUNIT)) return fail(ffi_code(re.kind), error_display(re.kind, re.msg));
+          gg_session* s = op->ses.get();
+          if (device_report_on(s) && s->fetched_on_device) {   // (chunk_tiles found no erroring tile)
+            // the chunk's suites rendered on its device (report_junit_kernel), frame-less
+            if (!device_report_text(s, 0, s->docs.ndocs(), SIZE_MAX, sink, re, nullptr, OUT_JUNIT, kStreamPushBlocks))
+              return fail(ffi_code(re.kind), error_display(re.kind, re.msg));
+            if (sink.failed) return fail(-1, "the write callback failed");
+            op->ses.reset();
+            continue;
+          }
+          if (!session_report(s, out, code, re, OUT_JUNIT)) return fail(ffi_code(re.kind), error_display(re.kind, re.msg));
           size_t a = out.find('\n');
           a = a == std::string::npos ? out.size() : out.find('\n', a + 1);
           a = a == std::string::npos ? out.size() : a + 1;
-          const size_t tl = sizeof(kTail) - 1;
-          const size_t b = out.size() >= a + tl && out.compare(out.size() - tl, tl, kTail) == 0 ? out.size() - tl : out.size();
+          const size_t tl = sizeof(kJunitTail) - 1;
+          const size_t b = out.size() >= a + tl && out.compare(out.size() - tl, tl, kJunitTail) == 0 ? out.size() - tl : out.size();
           if (b > a) sink.write(out.data() + a, b - a);
           if (sink.failed) return fail(-1, "the write callback failed");
           op->ses.reset();
         }
-        sink.write(kTail, sizeof(kTail) - 1);
+        sink.write(kJunitTail, sizeof(kJunitTail) - 1);
       }
     }
     if (sink.failed) return fail(-1, "the write callback failed");
@@ -3803,6 +3849,49 @@ int64_t gg_session_report_yaml_device(gg_session* s, size_t max_docs, int32_t* e
     bool anyfail = false;
     for (size_t t = 0; t < nd * nf; t++) if (s->tiles[t].status == ST_FAIL) anyfail = true;
     if (exit_code) *exit_code = anyfail ? 19 : (s->parse_errors.empty() ? 0 : 5);
+    if (stats) {
+      stats[0] = (double)st.device_docs; stats[1] = (double)st.host_docs; stats[2] = st.size_ms; stats[3] = st.write_ms;
+      stats[4] = st.d2h_ms; stats[5] = st.host_ms; stats[6] = (double)st.bytes; stats[7] = 0;
+    }
+    return bytes;
+  } catch (std::exception& e) { set_err(err, -1, e.what()); return -1; }
+}
+
+// The JUnit report of the first max_docs documents (0: all): the frame with its totals on the host, every
+// document's <testsuite> rendered on the device (report_junit_kernel), copied to host memory and dropped
+// (measurement, as gg_session_report_json_device; the same eight stats).  Returns the report's byte count.
+int64_t gg_session_report_junit_device(gg_session* s, size_t max_docs, int32_t* exit_code, double* stats, extern_err_t* err) {
+  set_err(err, 0, "");
+  if (!s->evaluated || !s->fetched_on_device) { set_err(err, -1, "session not evaluated and fetched on a device"); return -1; }
+  try {
+    std::vector<const Program*> progs;
+    for (auto& p : s->progs) progs.push_back(&p->prog);
+    const size_t nf = progs.size(), nd = max_docs ? std::min(max_docs, s->docs.ndocs()) : s->docs.ndocs();
+    size_t failures = 0;
+    for (size_t t = 0; t < nd * nf; t++) {
+      if (s->tiles[t].err) {
+        ensure_host_arena(s);
+        ReportError re;
+        tile_error(s->docs, (uint32_t)(t / nf), *progs[t % nf], s->tiles[t], re);
+        set_err(err, ffi_code(re.kind), error_display(re.kind, re.msg));
+        if (exit_code) *exit_code = -1;
+        return -1;
+      }
+      failures += s->tiles[t].status == ST_FAIL;
+    }
+    bind_device(s);
+    render_tables(s);
+    CountingSink sink(s->dv->pinned, DeviceBufs::kPinnedBytes);
+    DevReportStats st;
+    ReportError re;
+    if (!device_report_text(s, 0, nd, SIZE_MAX, sink, re, &st, OUT_JUNIT)) {
+      set_err(err, ffi_code(re.kind), error_display(re.kind, re.msg));
+      if (exit_code) *exit_code = -1;
+      return -1;
+    }
+    const int64_t bytes = (int64_t)(junit_head(nd * nf, failures).size() + sink.n + sizeof(kJunitTail) - 1);
+    // JunitReporter::update_exit_code keeps a rules-file parse error's 5 over 19
+    if (exit_code) *exit_code = !s->parse_errors.empty() ? 5 : (failures ? 19 : 0);
     if (stats) {
       stats[0] = (double)st.device_docs; stats[1] = (double)st.host_docs; stats[2] = st.size_ms; stats[3] = st.write_ms;
       stats[4] = st.d2h_ms; stats[5] = st.host_ms; stats[6] = (double)st.bytes; stats[7] = 0;

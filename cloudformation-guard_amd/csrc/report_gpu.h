@@ -16,6 +16,10 @@
 // record walk compiled with the block-YAML writer, scalar styles by yaml_scalar.h): one item of the root
 // sequence per document, the same passes, blocks and fallback; libyaml-only cases ("|+" literals, complex
 // keys) join the fallback list.
+//
+// The JUnit report (`-o junit`) is report_junit_kernel (report_junit_gpu.hip): one <testsuite> per document
+// through an XML-escaping writer, a FAILed tile's records walked twice (what the <failure> opening needs,
+// then the message texts); the same passes, blocks and fallback.
 #pragma once
 #include <stdint.h>
 
@@ -41,7 +45,8 @@ struct RProg {
   const char* lit_bytes;
   const uint32_t* lit_line;
   const uint32_t* lit_col;
-  uint32_t n_clauses, n_lit, n_rule_names, n_queries, n_ctx, n_msgs, pad0, pad1;
+  uint32_t n_clauses, n_lit, n_rule_names, n_queries, n_ctx, n_msgs;
+  RStr file_name;            // Program::file_name (the JUnit test case's name)
 };
 
 struct RenderArgs {

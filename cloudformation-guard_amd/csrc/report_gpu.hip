@@ -39,9 +39,9 @@ struct W {
 // (every writer function is inlined into the kernels: a W passed to a real call would live in scratch and
 // every byte would become scratch traffic; the byte-level functions stay trivial so the inlined kernels
 // compile in reasonable time)
-#ifdef GG_REPORT_YAML
-// (the YAML unit: the walk's larger functions are real calls -- each compiled once.  Inlined like the JSON
-// writer's, the one kernel compiles for 17 to 30 minutes; the byte-level functions stay inline)
+#if defined(GG_REPORT_YAML) || defined(GG_REPORT_JUNIT)
+// (the YAML and JUnit units: the walk's larger functions are real calls -- each compiled once.  Inlined like
+// the JSON writer's, the one YAML kernel compiles for 17 to 30 minutes; the byte-level functions stay inline)
 #define RN __device__ __attribute__((noinline))
 #else
 #define RN RD
@@ -179,6 +179,7 @@ template <class WT> RN void cmp(WT& w, uint32_t op, bool neg) {
   close(w, ']');
 }
 
+#ifndef GG_REPORT_JUNIT
 // ----------------------------------------------------------------------------- YAML writer ---
 // The same walk writes block YAML through Y: serde_yaml 0.9 over libyaml 0.2.5, width unlimited (reporter.cpp
 // YamlOut).  A scalar's style depends on the whole string, so every string runs through yaml_scalar.h twice:
@@ -335,6 +336,7 @@ RD void doc_begin(Y& y, bool) {
   raw(y, '-'); y.dash = true;
 }
 RD void doc_end(Y& y) { raw(y, '\n'); }
+#endif  // !GG_REPORT_JUNIT
 
 // ---------------------------------------------------------------------------------- values ---
 struct Ctx {
@@ -892,7 +894,7 @@ template <class WT> RN void tile_items(WT& w, const Ctx& c, const RecSeq recs, u
   while (sp && !w.fb) { close(w, ']'); close(w, '}'); close(w, '}'); sp--; }
 }
 
-#ifndef GG_REPORT_YAML
+#if !defined(GG_REPORT_YAML) && !defined(GG_REPORT_JUNIT)
 // ------------------------------------------------------------------------------- SARIF ---
 // SarifResults::from (sarif.rs:127-160) for one tile: every message of every ClauseReport
 // (ClauseReport::get_message, eval_context.rs:1808-1826 -- a Rule's and a Disjunction's checks flattened,
@@ -1113,7 +1115,7 @@ RN void file_sarif(W& w, const RenderArgs& A, uint32_t doc) {
   }
 }
 
-#endif  // !GG_REPORT_YAML
+#endif  // !GG_REPORT_YAML && !GG_REPORT_JUNIT
 
 // one document's FileReport (write_file_report), preceded by ",\n" after the report's first document and
 // the array's two-space indent
@@ -1161,7 +1163,7 @@ template <class WT> RN void file_report(WT& w, const RenderArgs& A, uint32_t doc
 
 }  // namespace rg
 
-#ifndef GG_REPORT_YAML
+#if !defined(GG_REPORT_YAML) && !defined(GG_REPORT_JUNIT)
 // One kernel for both passes (one instantiation of the inlined writer: it is large).  Size pass (write 0):
 // the bytes of each document of the block, or kHostDoc | reason for the host writer.  Write pass (write 1):
 // each device document at offsets[k] of the block's contiguous text.  Capped at 128 VGPRs (4 waves per
@@ -1191,7 +1193,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) r
     if (!write) A.sizes[k] = w.fb ? (kHostDoc | w.fb) : w.n;
   }
 }
-#else
+#elif defined(GG_REPORT_YAML)
 // The YAML report (rg::file_report through rg::Y): one lane per document, one item of the report's root
 // sequence each, in the same two passes and launch shape; compiled as a unit of its own
 // (report_yaml_gpu.hip) so the JSON and SARIF kernels above keep their code.

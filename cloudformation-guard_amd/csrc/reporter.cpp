@@ -1520,6 +1520,14 @@ bool ReportWriter::add(const DocBatch& docs, uint32_t doc, const std::vector<con
   return true;
 }
 
+bool junit_doc_suite(const DocBatch& docs, uint32_t doc, const std::vector<const Program*>& progs,
+                     const std::vector<const TileResult*>& tiles, std::string& out, ReportError& err) {
+  ReportWriter w(OUT_JUNIT);
+  if (!w.add(docs, doc, progs, tiles, err)) return false;
+  out += w.p_->suites;
+  return true;
+}
+
 void ReportWriter::absorb(ReportWriter& later) {
   Impl& I = *p_;
   Impl& L = *later.p_;

@@ -147,6 +147,8 @@ class ReportWriter {
   void absorb(ReportWriter& later);
 
  private:
+  friend bool junit_doc_suite(const DocBatch&, uint32_t, const std::vector<const Program*>&,
+                              const std::vector<const TileResult*>&, std::string&, ReportError&);
   struct Impl;
   Impl* p_;
 };
@@ -158,6 +160,11 @@ class ReportWriter {
 bool sarif_doc_results(const DocBatch& docs, uint32_t doc, const std::vector<const Program*>& progs,
                        const std::vector<const TileResult*>& tiles, std::string& out, ReportError& err);
 void sarif_frame(const std::vector<std::string>& artifact_names, std::string& head, std::string& tail);
+
+// JUnit around the device-rendered test suites (capi.cpp device_report_text): one document's <testsuite>
+// element as ReportWriter writes it, without the report's frame.
+bool junit_doc_suite(const DocBatch& docs, uint32_t doc, const std::vector<const Program*>& progs,
+                     const std::vector<const TileResult*>& tiles, std::string& out, ReportError& err);
 
 // The structured report of documents [first, first + ndocs) rendered on `nthreads` host threads over
 // contiguous document ranges; byte-identical to one ReportWriter fed in order.  tile(d, f) gives

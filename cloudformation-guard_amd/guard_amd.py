@@ -104,6 +104,9 @@ def lib():
     if hasattr(L, "gg_session_report_yaml_device"):
         L.gg_session_report_yaml_device.argtypes = L.gg_session_report_json_device.argtypes
         L.gg_session_report_yaml_device.restype = ctypes.c_int64
+    if hasattr(L, "gg_session_report_junit_device"):
+        L.gg_session_report_junit_device.argtypes = L.gg_session_report_json_device.argtypes
+        L.gg_session_report_junit_device.restype = ctypes.c_int64
         L.gg_yaml_scalar.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int32, ctypes.c_char_p,
                                      ctypes.c_size_t]
         L.gg_yaml_scalar.restype = ctypes.c_int64
@@ -694,8 +697,20 @@ class Session:
         keys = ("device_docs", "host_docs", "size_ms", "write_ms", "d2h_ms", "host_ms", "body_bytes")
         return n, code.value, dict(zip(keys, list(st)[:7]))
 
+    def report_junit_device(self, max_docs=0):
+        """the JUnit report of the first max_docs documents (0: all): test suites rendered on the device, copied to
+        host memory and discarded: (bytes, exit code, stats)"""
+        code = ctypes.c_int32(0)
+        st = (ctypes.c_double * 8)()
+        err = ExternError()
+        n = lib().gg_session_report_junit_device(self.s, max_docs, ctypes.byref(code), st, ctypes.byref(err))
+        if err.code != 0:
+            _raise(err)
+        keys = ("device_docs", "host_docs", "size_ms", "write_ms", "d2h_ms", "host_ms", "body_bytes")
+        return n, code.value, dict(zip(keys, list(st)[:7]))
+
     def set_device_report(self, on):
-        """JSON / YAML / SARIF reports rendered on the device (True), on host threads (False), or per GG_DEVICE_REPORT (None)"""
+        """JSON / YAML / SARIF / JUnit reports rendered on the device (True), on host threads (False), or per GG_DEVICE_REPORT (None)"""
         lib().gg_session_set_device_report(self.s, -1 if on is None else int(bool(on)))
 
     def report_shards(self, output="json", cuts=()):

@@ -268,7 +268,12 @@ int64_t gg_session_report_sarif_device(gg_session *s, size_t max_docs, int32_t *
  * document the device writer leaves to libyaml ("|+" scalars, complex keys, floats, ...) is written by the
  * host writer at its position. */
 int64_t gg_session_report_yaml_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
-/* JSON reports of this session (gg_session_report*, the batch entry points): 1 rendered on the device
+/* the JUnit report (`-o junit`: the frame and its totals on the host, one <testsuite> per document rendered
+ * on the device by csrc/report_junit_gpu.hip, byte for byte the host writer's text), counted; the same
+ * stats.  A document the device writer does not cover (floats, Debug-formatted reasons, nesting past 48, ...)
+ * is written by the host writer at its position. */
+int64_t gg_session_report_junit_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
+/* JSON / YAML / SARIF / JUnit reports of this session (gg_session_report*, the batch entry points): 1 rendered on the device
  * (default, GG_DEVICE_REPORT=0 turns it off), 0 on host threads, -1 back to the environment's choice. */
 int32_t gg_session_set_device_report(gg_session *s, int32_t on);
 /* diagnostic evaluator counters (nonzero only in the GG_STATS build variant) */
