@@ -34,6 +34,7 @@
 #include "json_gpu.h"
 #include "eisel_lemire.h"
 #include "yaml_scalar.h"
+#include "shortest_f64.h"
 #include "program.h"
 #include "report_gpu.h"
 #include "reporter.h"
@@ -1104,7 +1105,7 @@ unsigned report_threads() {
 // (context strings, messages, rule names, remaining-query texts, literal arena, sorted rule names) built
 // once per upload, the marks uploaded at first use, then per block of documents a size pass, offsets, a
 // write pass and the text copied out in document order, with the documents the device writer leaves to
-// the host (floats, Debug-formatted reasons, ...) written by the host writer at their positions.
+// the host (non-finite floats, Debug-formatted reasons, ...) written by the host writer at their positions.
 bool device_report_on(const gg_session* s) {
   if (s->device_report >= 0) return s->device_report != 0;
   const char* e = getenv("GG_DEVICE_REPORT");
@@ -4055,6 +4056,16 @@ int32_t gg_parse_f64(const char* s, size_t n, double* out) {
     return 0;
   memcpy(out, &bits, 8);
   return 1;
+}
+
+// the device report writers' float formatter (shortest_f64.h) on the host: the finite double with these IEEE
+// bits in style 0 (ryu / serde_json number) or 1 (Rust Display).  Returns the byte count written to
+// out[0..cap), -1 for NaN / infinity, an unknown style or a cap too small.
+int64_t gg_format_f64(uint64_t bits, int32_t style, char* out, size_t cap) {
+  if ((bits & 0x7FF0000000000000ull) == 0x7FF0000000000000ull || (style != 0 && style != 1)) return -1;
+  size_t n = 0;
+  sf::layout(sf::shortest_f64(bits, kPow10_128), style == 1, [&](char c) { if (n < cap) out[n] = c; n++; });
+  return n <= cap ? (int64_t)n : -1;
 }
 
 // the device YAML writer's scalar machine (yaml_scalar.h) on the host: `text` as it follows "k:" in a mapping

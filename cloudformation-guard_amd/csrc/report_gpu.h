@@ -7,7 +7,9 @@
 // (eval_context.rs:1965-2435 report_all_failed_clauses_for_rules / simplified_json_from_root), serde's
 // pretty layout (2-space indent, "[]" / "{}" when empty) and the message texts (Display of
 // PathAwareValue / UnResolved, display.rs:33-107).  One lane renders one document, twice: a size pass
-// and a write pass at the offsets their scan gives (pool strings read 16 bytes at a time).  A document the device writer does not cover (a float,
+// and a write pass at the offsets their scan gives (pool strings read 16 bytes at a time).  Floats are rendered by the lanes themselves
+// (shortest_f64.h: shortest round-trip digits in ryu's layout as values, Rust Display inside messages).  A document
+// the device writer does not cover (a NaN or infinite float,
 // Debug-formatted reasons, map keys or count() values as values, ranges / chars, nesting past 48) is
 // flagged in the size pass and written by the host writer at its position, so the bytes never depend on
 // which writer ran.

@@ -10,6 +10,8 @@
 
 #define GG_HD __host__ __device__ __attribute__((always_inline))
 #include "yaml_scalar.h"
+#define GG_POW10_QUAL __constant__
+#include "shortest_f64.h"
 
 namespace gg {
 namespace rg {
@@ -163,6 +165,22 @@ RD void kstr(W& w, const char* s, uint32_t n) { item(w); jstr(w, s, n); raw(w, '
 RD void jnull(W& w) { raws(w, "null"); }
 RD void jbool(W& w, bool b) { raws(w, b ? "true" : "false"); }
 RD void jint(W& w, int64_t v) { const bool e = w.esc; w.esc = false; ti64(w, v); w.esc = e; }
+// A float's shortest digits (shortest_f64.h): one real call per unit.  It takes the bits and returns digits,
+// exponent and sign in registers and never sees a writer, so the writer's pointer and count stay in registers
+// across it; each lane indexes the power-of-ten table (__constant__ memory: 9.9 KB, cache-resident) by its own
+// exponent with one 16-byte vector load.  The layouts stay inline at their call sites: one put site each.
+__device__ __attribute__((noinline)) sf::Dec64 shortest_call(uint64_t bits) { return sf::shortest_f64(bits, kPow10_128); }
+RD bool finite_bits(uint64_t bits) { return (bits & 0x7FF0000000000000ull) != 0x7FF0000000000000ull; }
+// a finite float in a message text: Rust Display through the text filters
+template <class WT> RD void tf64(WT& w, uint64_t bits) {
+  const sf::Dec64 d = shortest_call(bits);
+  sf::display_layout(d, [&](char c) __attribute__((always_inline)) { tput(w, c); });
+}
+// ... as a JSON number: ryu's text, raw
+RD void jfloat(W& w, uint64_t bits) {
+  const sf::Dec64 d = shortest_call(bits);
+  sf::ryu_layout(d, [&](char c) __attribute__((always_inline)) { raw(w, c); });
+}
 // a document's FileReport begins: ",\n" after the report's first, the root array's indent
 RD void doc_begin(W& w, bool first) {
   if (!first) { raw(w, ','); raw(w, '\n'); }
@@ -324,6 +342,11 @@ RD void jlit(Y& y, const char* s) { uint32_t n = 0; while (s[n]) n++; yscalar(y,
 RD void kstr(Y& y, const char* s, uint32_t n) { entry(y); yscalar(y, s, n, true); raw(y, ':'); y.dash = false; }
 RD void jnull(Y& y) { raws(y, " null"); }
 RD void jbool(Y& y, bool b) { raws(y, b ? " true" : " false"); }
+RD void jfloat(Y& y, uint64_t bits) {   // serde_yaml writes ryu's text plain: none of it needs quoting
+  const sf::Dec64 d = shortest_call(bits);
+  raw(y, ' ');
+  sf::ryu_layout(d, [&](char c) __attribute__((always_inline)) { raw(y, c); });
+}
 RD void jint(Y& y, int64_t v) {   // serde_yaml writes integers plain
   raw(y, ' ');
   y.emitting = true; y.sc.style = ys::PLAIN;
@@ -366,6 +389,7 @@ RD bool nv(const Ctx& c, uint32_t ref, NV& n) {
 RD const char* bytes_of(const Ctx& c, uint32_t ref) { return (ref & LIT_BIT) ? c.P->lit_bytes : c.A->pool; }
 RD uint32_t child(uint32_t ref, const NV& n, uint32_t j) { return (ref & LIT_BIT) | (n.a + j); }
 RD int64_t ival(const NV& n) { return (int64_t)(((uint64_t)n.b << 32) | n.a); }
+RD uint64_t fbits(const NV& n) { return ((uint64_t)n.b << 32) | n.a; }
 RD uint32_t line_of(const Ctx& c, uint32_t ref) { return (ref & LIT_BIT) ? c.P->lit_line[ref & ~LIT_BIT] : c.A->line[c.dbase + ref]; }
 RD uint32_t col_of(const Ctx& c, uint32_t ref) { return (ref & LIT_BIT) ? c.P->lit_col[ref & ~LIT_BIT] : c.A->col[c.dbase + ref]; }
 
@@ -437,7 +461,10 @@ template <class WT> RN void write_value(WT& w, const Ctx& c, uint32_t ref) {
         sref[sp] = cur; sj[sp] = 0; sp++;
         entered = true;
         break;
-      case K_FLOAT: w.fb = FB_FLOAT; return;
+      case K_FLOAT:   // NaN / inf: the host writer raises its IncompatibleError
+        if (!finite_bits(fbits(n))) { w.fb = FB_FLOAT; return; }
+        jfloat(w, fbits(n));
+        break;
       default: w.fb = FB_KIND; return;
     }
     (void)entered;
@@ -485,7 +512,10 @@ template <class WT> RN void value_only(WT& w, const Ctx& c, uint32_t ref) {
         tput(w, n.kind == K_LIST ? '[' : '{');
         sref[sp] = cur; sj[sp] = 0; sp++;
         break;
-      case K_FLOAT: w.fb = FB_FLOAT; return;
+      case K_FLOAT:
+        if (!finite_bits(fbits(n))) { w.fb = FB_FLOAT; return; }
+        tf64(w, fbits(n));
+        break;
       default: w.fb = FB_KIND; return;
     }
     if (w.fb) return;

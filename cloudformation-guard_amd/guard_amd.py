@@ -12,6 +12,7 @@ HIP device is present, calls raise -- there is no CPU fallback.
 """
 import ctypes
 import os
+import struct
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GG_LIB selects a diagnostic build variant (e.g. libcfnguard_mi355x_stats.so); default: the product library
@@ -206,6 +207,9 @@ def lib():
     L.gg_regex_match.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
     L.gg_parse_f64.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_double)]
     L.gg_regex_match.restype = ctypes.c_int32
+    if hasattr(L, "gg_format_f64"):   # (absent from builds before the device float writer: GG_LIB A/B)
+        L.gg_format_f64.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_char_p, ctypes.c_size_t]
+        L.gg_format_f64.restype = ctypes.c_int64
     L.gg_session_report_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(ExternError)]
     L.gg_session_report_bytes.restype = ctypes.c_int64
@@ -230,6 +234,15 @@ def parse_f64(text):
     b = _b(text)
     out = ctypes.c_double(0)
     return out.value if lib().gg_parse_f64(b, len(b), ctypes.byref(out)) == 1 else None
+
+
+def format_f64(x, style=0):
+    """the device report writers' float formatter on the host: the text of the float x in style 0 (ryu: a
+    serde_json / serde_yaml number) or 1 (Rust Display, as inside messages); None for NaN / infinity"""
+    bits = struct.unpack("<Q", struct.pack("<d", x))[0]
+    buf = ctypes.create_string_buffer(336)
+    n = lib().gg_format_f64(bits, style, buf, len(buf))
+    return None if n < 0 else buf.raw[:n].decode("ascii")
 
 
 def yaml_scalar(text, indent=0, is_key=False):

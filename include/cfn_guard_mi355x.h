@@ -256,7 +256,8 @@ int64_t gg_session_report_bytes(gg_session *s, int32_t output_format, size_t max
 /* The structured JSON report of the first max_docs documents (0: all) rendered on the session's device
  * (csrc/report_gpu.hip: a size pass and a write pass per block of documents, one lane per document), copied
  * to host memory block by block and discarded; documents the device writer leaves to the host writer
- * (floats, Debug-formatted reasons, map keys / count() values as values) are written by it in place.
+ * (non-finite floats, Debug-formatted reasons, map keys / count() values as values) are written by it in place;
+ * finite floats are rendered on the device in every format (csrc/shortest_f64.h).
  * Returns the report's size in bytes (gg_session_report_bytes' end-to-end measurement, reporter on the
  * device); stats (may be NULL, 8 doubles): device documents, host documents, size-pass ms, write-pass ms,
  * copy-out ms, host-writer ms, body bytes, 0. */
@@ -265,12 +266,12 @@ int64_t gg_session_report_json_device(gg_session *s, size_t max_docs, int32_t *e
 int64_t gg_session_report_sarif_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
 /* the YAML report (`-o yaml`: one item of the root sequence per document, rendered on the device by
  * csrc/report_yaml_gpu.hip, byte for byte the host libyaml writer's text), counted; the same stats.  A
- * document the device writer leaves to libyaml ("|+" scalars, complex keys, floats, ...) is written by the
+ * document the device writer leaves to libyaml ("|+" scalars, complex keys, non-finite floats, ...) is written by the
  * host writer at its position. */
 int64_t gg_session_report_yaml_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
 /* the JUnit report (`-o junit`: the frame and its totals on the host, one <testsuite> per document rendered
  * on the device by csrc/report_junit_gpu.hip, byte for byte the host writer's text), counted; the same
- * stats.  A document the device writer does not cover (floats, Debug-formatted reasons, nesting past 48, ...)
+ * stats.  A document the device writer does not cover (non-finite floats, Debug-formatted reasons, nesting past 48, ...)
  * is written by the host writer at its position. */
 int64_t gg_session_report_junit_device(gg_session *s, size_t max_docs, int32_t *exit_code, double *stats, extern_err_t *err);
 /* JSON / YAML / SARIF / JUnit reports of this session (gg_session_report*, the batch entry points): 1 rendered on the device
@@ -328,6 +329,11 @@ int32_t gg_session_add_synthetic_device_fmt(gg_session *s, uint64_t first, size_
 /* Host diagnostic: the device loader's float parser (Eisel-Lemire, csrc/eisel_lemire.h) on the JSON
  * number s[0..n): 1 = *out is the correctly rounded double, 0 = refused (its document loads on the host). */
 int32_t gg_parse_f64(const char *s, size_t n, double *out);
+/* Host diagnostic: the device report writers' float formatter (Schubfach shortest digits, csrc/shortest_f64.h)
+ * on the finite double with these IEEE bits, style 0 = ryu (serde_json / serde_yaml number: 2.5, 1e21, -0.0),
+ * 1 = Rust Display (no exponent: 1000000000000000000000, -0).  Returns the bytes written to out[0..cap),
+ * -1 for NaN / infinity (the host writer's cases), an unknown style or a cap too small (330 always fits). */
+int64_t gg_format_f64(uint64_t bits, int32_t style, char *out, size_t cap);
 /* Host diagnostic: the device YAML writer's scalar machine (csrc/yaml_scalar.h) on `text`, as it follows
  * "k:" in a mapping whose keys sit at column `indent` (separating space, scalar, no final break) or, with
  * is_key, as that mapping's key.  Returns the bytes written to out, -1 = the device writer leaves the
