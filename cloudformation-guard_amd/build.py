@@ -25,8 +25,8 @@ YAML_LIB = "/opt/conda/lib"
 
 HOST_SRCS = ["doc_loader.cpp", "rules_parser.cpp", "regex_dfa.cpp", "cruet.cpp", "compiler.cpp", "reporter.cpp",
              "synth_corpus.cpp"]
-HIP_SRCS = ["eval_kernel.hip", "eval_kernel_nfa.hip", "json_gpu.hip", "report_gpu.hip", "report_yaml_gpu.hip", "report_junit_gpu.hip",
-            "order_sort.hip", "capi.cpp"]
+HIP_SRCS = ["eval_kernel.hip", "eval_kernel_nfa.hip", "json_gpu.hip", "merge_gpu.hip", "report_gpu.hip", "report_yaml_gpu.hip",
+            "report_junit_gpu.hip", "order_sort.hip", "capi.cpp"]
 # occupancy target of the lane-mode kernel (waves per SIMD); it caps VGPRs at 512 / N.  4 (126 VGPRs,
 # 8 spilled) beats 2 (178) and 3 (168): the kernel waits on dependent loads, so resident waves are
 # worth more than registers (profiles/r02_ab_occupancy.log; capi.cpp sizes the grid to 16 waves/CU)
@@ -49,6 +49,7 @@ SRC_FLAGS["eval_kernel_nfa.hip"] = SRC_FLAGS["eval_kernel.hip"]
 # the YAML report writer holds no float code; packed-fp32 forms are kept out of new units all the same
 SRC_FLAGS["report_yaml_gpu.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS["report_junit_gpu.hip"] = SRC_FLAGS["report_yaml_gpu.hip"]
+SRC_FLAGS["merge_gpu.hip"] = SRC_FLAGS["report_yaml_gpu.hip"]
 
 
 def _obj(obj_dir, s):

@@ -1968,15 +1968,20 @@ char* cfn_guard_validate_batch_format(const validate_input_t* docs, size_t n_doc
   return cfn_guard_validate_batch_params(docs, n_docs, rules, n_rules, nullptr, 0, output_format, exit_code, err);
 }
 
-// The batch entries load a batch of at least GG_BATCH_DEVICE_LOAD_MIN documents (64; 0 = never) without input
-// parameters with the device loader (JSON and block-style YAML on the MI355X, the rest on host threads at
-// their positions); when that path does not take the whole batch -- too few large documents, a document
-// the host loader then rejects -- the documents load one by one on the host as before, so a load error is
-// still the first failing document's, with the reference's message.
-static bool batch_device_load(gg_session* s, const validate_input_t* docs, size_t n_docs, size_t first, size_t count) {
+static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char* const* texts, const size_t* lens,
+                               const char* const* names, size_t n, double* stats, extern_err_t* err);
+
+// The batch entries load a batch of at least GG_BATCH_DEVICE_LOAD_MIN documents (64; 0 = never) with the
+// device loader (JSON and block-style YAML on the MI355X, the rest on host threads at their positions; input
+// parameters -- `params`, or the session's -- merged there too); when that path does not take the whole batch
+// -- too few large documents, a document the host loader then rejects, a parameter merge that fails -- the
+// documents load one by one on the host as before, so an error is still the first failing document's, with
+// the reference's message and precedence.
+static bool batch_device_load(gg_session* s, const validate_input_t* docs, size_t n_docs, size_t first, size_t count,
+                              const DocBatch* params = nullptr) {
   const char* e = getenv("GG_BATCH_DEVICE_LOAD_MIN");
   const size_t min_docs = e ? (size_t)std::max(0, atoi(e)) : 64;
-  if (!min_docs || count < min_docs || s->params || s->docs.ndocs()) return false;
+  if (!min_docs || count < min_docs || s->docs.ndocs()) return false;
   (void)n_docs;
   std::vector<const char*> t(count), nm(count);
   std::vector<size_t> l(count);
@@ -1991,7 +1996,9 @@ static bool batch_device_load(gg_session* s, const validate_input_t* docs, size_
     }
   });
   extern_err_t le{0, nullptr};
-  const int32_t rc = gg_session_add_docs_device(s, t.data(), l.data(), nm.data(), count, nullptr, &le);
+  // a parameter merge that fails on the device (rc -1) sends the batch to the one-by-one path as well: it
+  // words the error with the reference's precedence (first unloadable document, then parameter-file errors)
+  const int32_t rc = add_docs_device(s, params ? params : s->params.get(), t.data(), l.data(), nm.data(), count, nullptr, &le);
   if (le.message) free(le.message);
   return rc == 0;
 }
@@ -2022,7 +2029,7 @@ char* cfn_guard_validate_batch_params(const validate_input_t* docs, size_t n_doc
     const bool params_ok = load_params(params, n_params, s.params, pe);
     LoadError panic;
     bool panicked = false;
-    const bool on_device = !n_params && batch_device_load(&s, docs, n_docs, 0, n_docs);
+    const bool on_device = params_ok && batch_device_load(&s, docs, n_docs, 0, n_docs);
     for (size_t i = 0; i < n_docs && !on_device; i++) {
       LoadError le;
       const char* t = docs[i].content ? docs[i].content : "";
@@ -2095,7 +2102,7 @@ char* validate_batch_devices(const validate_input_t* docs, size_t n_docs, const 
       if (!add_rules(&S.s, rules[i].content ? rules[i].content : "", name, perr))
         S.s.parse_errors.push_back("Parsing error handling rule file = " + name + ", Error = " + error_display("ParseError", perr) + "\n---");
     }
-    const bool on_device = !n_params && batch_device_load(&S.s, docs, n_docs, starts[k], starts[k + 1] - starts[k]);
+    const bool on_device = params_ok && batch_device_load(&S.s, docs, n_docs, starts[k], starts[k + 1] - starts[k], pbatch.get());
     for (size_t i = starts[k]; i < starts[k + 1] && !on_device; i++) {
       const char* t = docs[i].content ? docs[i].content : "";
       if (!load_document(S.s.docs, t, lens[i], docs[i].file_name ? docs[i].file_name : "", LOAD_LIBYAML, S.le)) {
@@ -2735,8 +2742,9 @@ bool first_load_error(const validate_input_t* docs, size_t from, size_t n, std::
   return false;
 }
 
-// stream_chunk_session with input parameters: documents on the host loader, each merged with them; a merge
-// panic is returned as the chunk's error (panic = true) unless a later document of the chunk does not load
+// stream_chunk_session with input parameters: the chunk on the device loader with the parameters merged
+// there, or (a chunk it does not take, a merge that fails) documents on the host loader, each merged with them;
+// a merge panic is returned as the chunk's error (panic = true) unless a later document of the chunk does not load
 std::unique_ptr<gg_session> stream_chunk_session_params(int dev, const validate_input_t* docs, size_t n_docs,
                                                         const validate_input_t* rules, size_t n_rules, const DocBatch* params,
                                                         size_t first, size_t count, std::string& kind, std::string& msg,
@@ -2754,7 +2762,8 @@ std::unique_ptr<gg_session> stream_chunk_session_params(int dev, const validate_
   }
   LoadError pan;
   bool panicked = false;
-  for (size_t i = first; i < first + count; i++) {
+  const bool on_device = batch_device_load(ses.get(), docs, n_docs, first, count, params);
+  for (size_t i = first; i < first + count && !on_device; i++) {
     LoadError le;
     const char* t = docs[i].content ? docs[i].content : "";
     if (!load_document(ses->docs, t, strlen(t), docs[i].file_name ? docs[i].file_name : "", LOAD_LIBYAML, le)) {
@@ -4194,12 +4203,19 @@ static void load_stats(const GpuLoadStats& st, double* out) {
 
 int32_t gg_session_add_docs_device(gg_session* s, const char* const* texts, const size_t* lens, const char* const* names,
                                    size_t n, double* stats, extern_err_t* err) {
+  return add_docs_device(s, s->params.get(), texts, lens, names, n, stats, err);
+}
+
+// gg_session_add_docs_device with the input parameters given (a shard's or a chunk's session shares one
+// read-only parameter batch): they are merged into every document on the device (merge_gpu.h), into the
+// documents the device refuses on the host; a failing merge is the first failing document's, code -1
+static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char* const* texts, const size_t* lens,
+                               const char* const* names, size_t n, double* stats, extern_err_t* err) {
   set_err(err, 0, "");
   try {
     std::string why;
     if (!ensure_device(why, s->device, &s->device)) { set_err(err, -1, why); return -1; }
     if (s->docs.ndocs()) { set_err(err, 18, "IllegalArguments: the device loader fills an empty session"); return -1; }
-    if (s->params) { set_note(err, "input parameters are merged by the host loader (gg_session_add_docs)"); return 1; }
     // the device parse is one lane per document: a batch of few, large documents (Terraform plans of
     // thousands of resources) leaves the device nearly idle -- 2048 plans parsed at 0.3 GB/s of text
     // (profiles/r04a_bench_cfg4_lane_2048.json) against ~1 GB/s on 16 host threads -- so such a batch is
@@ -4224,12 +4240,15 @@ int32_t gg_session_add_docs_device(gg_session* s, const char* const* texts, cons
     ResidentArena res;
     const bool keep = !getenv("GG_RESIDENT_ARENA") || atoi(getenv("GG_RESIDENT_ARENA")) != 0;
     const auto tl = std::chrono::steady_clock::now();
-    if (!gpu_load_json(b, texts, lens, nm, n, st, why, &refused, &dev_nodes, keep ? &res : nullptr)) { set_note(err, why); return 1; }
+    ParamMerge pm;
+    pm.params = params;
+    if (!gpu_load_json(b, texts, lens, nm, n, st, why, &refused, &dev_nodes, keep ? &res : nullptr, &pm)) { set_note(err, why); return 1; }
     struct ResHolder { ResidentArena& r; ~ResHolder() { for (uint32_t* p : {r.line, r.col, r.kline, r.kcol}) dev_free(p); } } rhold{res};
     if (getenv("GG_LOAD_TRACE"))
       fprintf(stderr, "[load] gpu_load_json returned %8.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl).count());
     struct Holder { void*& p; ~Holder() { dev_free(p); } } hold{dev_nodes};
     const size_t dev_n = b.nodes.size();
+    LoadError host_panic;   // a host-built document's merge failure, when it precedes the device's
     if (!refused.empty()) {
       // the documents the device refused, built by the host loader (libyaml) on host threads and
       // spliced in at their positions: their nodes are appended to the arena, strings re-interned
@@ -4238,20 +4257,34 @@ int32_t gg_session_add_docs_device(gg_session* s, const char* const* texts, cons
       std::vector<DocBatch> parts(nt);
       std::vector<LoadError> errs(nt);
       std::vector<int> ok(nt, 1);
+      // the parameters are merged into each in its part batch; a part's first failing merge competes with
+      // the device's by document index (a document that does not load still refuses the batch first)
+      std::vector<LoadError> panics(nt);
+      std::vector<uint32_t> panic_doc(nt, NONE);
       parallel_run(nt, [&](size_t t) {
         for (size_t j = refused.size() * t / nt; j < refused.size() * (t + 1) / nt && ok[t]; j++) {
           const uint32_t d = refused[j];
           if (!load_document(parts[t], texts[d], lens[d], nm[d], LOAD_LIBYAML, errs[t])) ok[t] = 0;
+          else if (panic_doc[t] == NONE && !merge_params_last(parts[t], params, panics[t])) panic_doc[t] = d;
         }
       });
       for (size_t t = 0; t < nt; t++)
         if (!ok[t]) { set_note(err, "host loader: " + error_display(errs[t].kind, errs[t].msg)); return 1; }
+      for (size_t t = 0; t < nt; t++)
+        if (panic_doc[t] < pm.fail_doc) { pm.fail_doc = panic_doc[t]; host_panic = panics[t]; }
       merge_batches(b, parts);
       for (size_t j = 0; j < refused.size(); j++) {
         b.roots[refused[j]] = b.roots[n + j];
         b.base[refused[j]] = b.base[n + j];
       }
       b.roots.resize(n); b.base.resize(n); b.names.resize(n);
+    }
+    if (pm.fail_doc != NONE) {
+      // structured.rs:51-65 unwraps the merge: a panic, code -1, and the session stays empty
+      LoadError le = host_panic;
+      if (le.kind.empty()) { le.kind = "Panic"; le.msg = "called `Result::unwrap()` on an `Err` value: " + merge_error_debug(pm.fail); }
+      set_err(err, ffi_code(le.kind), error_display(le.kind, le.msg));
+      return -1;
     }
     s->docs = std::move(b);
     s->uploaded = false;

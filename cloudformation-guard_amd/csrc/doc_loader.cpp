@@ -1097,13 +1097,11 @@ bool load_document(DocBatch& b, const char* text, size_t len, const std::string&
 }
 
 // ------------------------------------------------------ input parameters ---
-namespace {
 const char* merge_type_info(uint32_t k) {   // PathAwareValue::type_info (path_value.rs:985-1000)
   static const char* t[] = {"null", "String", "Regex", "bool", "int", "float", "char", "array", "map",
                             "range(int, int)", "range(float, float)", "range(char, char)"};
   return k < 12 ? t[k] : "?";
 }
-}  // namespace
 
 bool merge_into_last(DocBatch& b, size_t d, const DocBatch& P, size_t pd, LoadError& err) {
   const uint64_t base = b.base[d];

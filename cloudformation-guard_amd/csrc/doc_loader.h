@@ -131,5 +131,7 @@ constexpr uint32_t kKeyPathExt = 0x80000000u;
 // root (b.roots[d]).  Returns false with err = MultipleValues / IncompatibleError (the reference's
 // messages) and b unchanged.
 bool merge_into_last(DocBatch& b, size_t d, const DocBatch& P, size_t pd, LoadError& err);
+// the type names of its IncompatibleError (PathAwareValue::type_info)
+const char* merge_type_info(uint32_t kind);
 
 }  // namespace gg

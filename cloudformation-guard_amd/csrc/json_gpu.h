@@ -44,8 +44,20 @@ struct ResidentArena {
   uint32_t* kcol = nullptr;
   uint64_t nodes = 0;          // 0: the columns came down to the host (out is complete)
 };
+//
+// With `merge` (and merge->params) the input parameters' document 0 is merged into every accepted document
+// on the device (merge_gpu.h): each document's nodes are followed by the tail merge_into_last appends, its
+// root is the merged root, and the arena is the one the host loader + merge_into_last build.  A refused
+// document keeps its placeholder, unmerged: the caller merges the one it builds.  When a document's
+// merge fails the load still returns true with the first such document (in document order) in
+// merge->fail_doc and the reference's error in merge->fail; the batch is then not to be evaluated.
+struct ParamMerge {
+  const DocBatch* params = nullptr;
+  uint32_t fail_doc = NONE;
+  LoadError fail;
+};
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused = nullptr,
-                   void** keep_nodes = nullptr, ResidentArena* resident = nullptr);
+                   void** keep_nodes = nullptr, ResidentArena* resident = nullptr, ParamMerge* merge = nullptr);
 
 }  // namespace gg

@@ -32,6 +32,7 @@
 #include "eisel_lemire.h"
 #include "dev_cache.h"
 #include "host_pinned.h"
+#include "merge_gpu.h"
 
 #include <algorithm>
 #include <chrono>
@@ -840,7 +841,9 @@ __global__ void __launch_bounds__(256) root_resources_kernel(const DNode* nodes,
 
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused,
-                   void** keep_nodes, ResidentArena* resident) {
+                   void** keep_nodes, ResidentArena* resident, ParamMerge* merge) {
+  if (merge && !merge->params) merge = nullptr;
+  if (merge) merge->fail_doc = NONE;
   if (resident) *resident = ResidentArena{};
   if (!keep_nodes) resident = nullptr;   // the columns stay only beside the nodes
   static const char* kWhy[] = {"", "outside the strict-JSON subset", "nesting deeper than 64", "duplicate map keys",
@@ -940,13 +943,26 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   JCHK(hipMemcpy(nn.data(), d_nn.p, n * 4, hipMemcpyDeviceToHost));
   JCHK(hipMemcpy(nc.data(), d_nc.p, n * 4, hipMemcpyDeviceToHost));
   JCHK(hipMemcpy(ns.data(), d_ns.p, n * 4, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> nbase(n);
+  // input parameters: every accepted document is followed by the tail the merge appends (merge_gpu.h),
+  // sized from its root's child count; without parameters the tail is zero
+  MergeTemplate tmpl;
+  std::vector<uint32_t> rc;
+  if (merge) {
+    merge_shape(*merge->params, tmpl);
+    DevArr<uint32_t> d_rc; d_rc.alloc(n);
+    merge_root_counts(d_counts.p, d_off.p, d_nc.p, d_doc_bad.p, (uint32_t)n, d_rc.p);
+    rc.resize(n);
+    JCHK(hipMemcpy(rc.data(), d_rc.p, n * 4, hipMemcpyDeviceToHost));
+  }
+  std::vector<uint64_t> nbase(n + 1);
   uint64_t N = 0, S = 0;
   for (size_t k = 0; k < n; k++) {
-    if (nn[k] > kMaxDocNodes) { why = kWhy[BAD_SIZE]; return false; }
+    const uint64_t tail = merge && rc[k] != NONE ? tmpl.tail(rc[k]) : 0;
+    if (nn[k] + tail > kMaxDocNodes) { why = kWhy[BAD_SIZE]; return false; }
     nbase[k] = N;
-    N += nn[k]; S += ns[k];
+    N += nn[k] + tail; S += ns[k];
   }
+  nbase[n] = N;
   // the host columns are sized (page faults, seconds at 1M documents) while the device passes run; one
   // thread per column.  A device-resident arena sizes them only if a document is refused (the host
   // loader's documents are merged into host columns).
@@ -961,8 +977,8 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } join_resizer{resizer};
   mark("count D2H + scan");
   DevArr<uint64_t> d_nbase;
-  d_nbase.alloc(n);
-  JCHK(hipMemcpy(d_nbase.p, nbase.data(), n * 8, hipMemcpyHostToDevice));
+  d_nbase.alloc(n + 1);
+  JCHK(hipMemcpy(d_nbase.p, nbase.data(), (n + 1) * 8, hipMemcpyHostToDevice));
   DevArr<DNode> d_nodes; d_nodes.alloc(N);
   DevArr<uint32_t> d_line, d_col, d_kline, d_kcol;
   d_line.alloc(N); d_col.alloc(N); d_kline.alloc(N); d_kcol.alloc(N);
@@ -1068,31 +1084,33 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   JCHK(hipMemcpy(&pool_used, d_pool_cursor.p, 8, hipMemcpyDeviceToHost));
   mark("pre-join");
   if (resident && refused && !refused->empty()) resident = nullptr;   // host documents join: host columns
-  if (resident) {
-    resident->line = d_line.p; resident->col = d_col.p; resident->kline = d_kline.p; resident->kcol = d_kcol.p;
-    resident->nodes = N;
-    d_line.p = d_col.p = d_kline.p = d_kcol.p = nullptr;
-  } else {
-    if (resizer.joinable()) resizer.join(); else size_columns();
-    mark("columns sized");
-    stg.d2h(out.nodes.data(), d_nodes.p, N * sizeof(DNode));
-    stg.d2h(out.line.data(), d_line.p, N * 4);
-    stg.d2h(out.col.data(), d_col.p, N * 4);
-    stg.d2h(out.kline.data(), d_kline.p, N * 4);
-    stg.d2h(out.kcol.data(), d_kcol.p, N * 4);
-  }
-  out.bytes.resize(pool_used);
-  if (pool_used) stg.d2h(&out.bytes[0], d_pool.p, pool_used);
-  mark("arena D2H");
-  std::vector<unsigned long long> tkey(tslots);
-  std::vector<uint32_t> tlen(tslots), tid(tslots);
-  JCHK(hipMemcpy(tkey.data(), d_tkey.p, tslots * 8, hipMemcpyDeviceToHost));
-  JCHK(hipMemcpy(tlen.data(), d_tlen.p, tslots * 4, hipMemcpyDeviceToHost));
-  JCHK(hipMemcpy(tid.data(), d_tid.p, tslots * 4, hipMemcpyDeviceToHost));
-  st.d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  mark("table D2H");
+  auto fetch_columns = [&]() {
+    if (resident) {
+      resident->line = d_line.p; resident->col = d_col.p; resident->kline = d_kline.p; resident->kcol = d_kcol.p;
+      resident->nodes = N;
+      d_line.p = d_col.p = d_kline.p = d_kcol.p = nullptr;
+    } else {
+      if (resizer.joinable()) resizer.join(); else size_columns();
+      mark("columns sized");
+      stg.d2h(out.nodes.data(), d_nodes.p, N * sizeof(DNode));
+      stg.d2h(out.line.data(), d_line.p, N * 4);
+      stg.d2h(out.col.data(), d_col.p, N * 4);
+      stg.d2h(out.kline.data(), d_kline.p, N * 4);
+      stg.d2h(out.kcol.data(), d_kcol.p, N * 4);
+    }
+  };
   uint64_t distinct = 0;
-  {
+  auto fetch_pool_index = [&]() {
+    out.bytes.resize(pool_used);
+    if (pool_used) stg.d2h(&out.bytes[0], d_pool.p, pool_used);
+    mark("arena D2H");
+    std::vector<unsigned long long> tkey(tslots);
+    std::vector<uint32_t> tlen(tslots), tid(tslots);
+    JCHK(hipMemcpy(tkey.data(), d_tkey.p, tslots * 8, hipMemcpyDeviceToHost));
+    JCHK(hipMemcpy(tlen.data(), d_tlen.p, tslots * 4, hipMemcpyDeviceToHost));
+    JCHK(hipMemcpy(tid.data(), d_tid.p, tslots * 4, hipMemcpyDeviceToHost));
+    st.d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    mark("table D2H");
     std::vector<uint32_t> aoff, alen;
     aoff.reserve(tslots / 2); alen.reserve(tslots / 2);
     for (uint64_t s = 0; s < tslots; s++) if (tkey[s]) { aoff.push_back(tid[s]); alen.push_back(tlen[s]); }
@@ -1100,9 +1118,43 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     mark("table scan");
     out.adopt_bulk(aoff.data(), alen.data(), aoff.size(), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
     mark("index built");
+  };
+  if (!merge) {
+    fetch_columns();
+    fetch_pool_index();
+  } else {
+    // the parameters' strings are interned into the batch's pool on the host (the pool and its index come
+    // down anyway; new strings append), then the merge fills every document's tail in the unpacked arena
+    // before a column leaves the device
+    fetch_pool_index();
+    if (out.bytes.size() + merge->params->bytes.size() > kMaxPoolBytes) {
+      if (resizer.joinable()) resizer.join();
+      out.clear();
+      why = kWhy[BAD_POOL];
+      return false;
+    }
+    merge_template(out, *merge->params, tmpl);
+    MergeArena MA{d_nodes.p, d_line.p, d_col.p, d_kline.p, d_kcol.p, d_nbase.p, d_nn.p, d_doc_bad.p, (uint32_t)n};
+    MergeFail mf;
+    const float mms = merge_params_device(MA, tmpl, mf);
+    st.kernel_ms += mms;
+    if (trace) fprintf(stderr, "[load] %-22s %8.3f ms (kernel)\n", "parameter merge", mms);
+    mark("parameter merge");
+    if (mf.doc != NONE && (mf.lost || mf.why == MERGE_LAYOUT)) {
+      if (resizer.joinable()) resizer.join();
+      out.clear();
+      why = mf.lost ? "parameter merge: more failing documents than the device records" : "parameter merge: a document's root does not match its reserved tail";
+      return false;
+    }
+    if (mf.doc != NONE) { merge->fail_doc = mf.doc; merge_fail_error(out, tmpl, mf, merge->fail); }
+    const auto tc = std::chrono::steady_clock::now();
+    fetch_columns();
+    st.d2h_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc).count();
   }
   out.roots.assign(n, 0);
-  out.base.assign(nbase.begin(), nbase.end());
+  if (merge)   // a merged document's root follows its own nodes and the parameters' (refused documents: the host's)
+    for (size_t k = 0; k < n; k++) if (!doc_bad[k]) out.roots[k] = nn[k] + tmpl.np;
+  out.base.assign(nbase.begin(), nbase.begin() + n);
   out.names.assign(names.begin(), names.begin() + n);
   st.nodes = N; st.distinct_strings = distinct; st.pool_bytes = pool_used;
   mark("adopt + names");

@@ -318,7 +318,13 @@ int32_t gg_session_add_synthetic(gg_session *s, uint64_t first, size_t n, int32_
  * says why; gg_session_add_docs reports the loader error), -1 on error.  stats (may be NULL, 10 doubles):
  * kernel ms, nodes, distinct strings, pool bytes, text bytes, H2D ms, D2H ms, intern-table doublings,
  * documents built by the host loader, host text-generation ms (gg_session_add_synthetic_device; else 0).  The loaded nodes stay in HBM for the session's first upload
- * (it packs the device arena from them; only host-built documents cross PCIe again). */
+ * (it packs the device arena from them; only host-built documents cross PCIe again).
+ * Input parameters set before (gg_session_set_params) are merged into every document on the device, in
+ * the loader's arena (PathAwareValue::merge, path_value.rs:889-919; structured.rs:51-65), and on the
+ * host into the documents the host loader builds: the session ends with the documents gg_session_add_docs
+ * builds.  kernel ms then includes the merge kernel.  A merge that fails (a root key the parameters hold
+ * too, root kinds that differ) is the first failing document's in document order: -1 with the
+ * reference's panic message, and the session stays empty. */
 int32_t gg_session_add_docs_device(gg_session *s, const char *const *texts, const size_t *lens, const char *const *names,
                                    size_t n, double *stats, extern_err_t *err);
 int32_t gg_session_add_synthetic_device(gg_session *s, uint64_t first, size_t n, int32_t n_resources, int32_t nthreads,
