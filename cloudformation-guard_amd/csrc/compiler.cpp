@@ -1,4 +1,5 @@
 // Rules AST -> flat device program (see program.h).
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -680,6 +681,66 @@ struct Compiler {
       if (pp.kind == P_VAR_HEAD) pp.c = scoped[pp.a] ? 0u : 1u;
   }
 
+  // Prefix-memo slots (eval_core.inc, "Prefix memo"): the access clauses' queries that walk the same run of plain
+  // key steps right after the same `%var` head share a slot, PQuery.pad bits 8-15 = slot + 1, bits 16-23 = steps in
+  // the run.  The variable is one the walker reads from the root table (mark_root_vars) that a root query or
+  // function let defines and nothing captures into, so its value list is fixed once resolved.  A run ends before
+  // the first step that is not a plain key (filter, index, `*`, `[*]`, `%var` key); each query takes the longest
+  // run it shares with another one, and the slots (guard_types.h kPrefixSlots) go to the runs that save the most steps.
+  void mark_prefix_slots() {
+    std::vector<uint8_t> fixed(P.var_names.size(), 0);
+    const PBlock& rb = blocks[P.hdr.root_block];
+    for (uint32_t i = 0; i < rb.nlets; i++) {
+      const PLet& l = lets[rb.first_let + i];
+      if (l.kind != L_LITERAL) fixed[l.var] = 1;
+    }
+    for (auto& pp : parts) {
+      if ((pp.kind == P_ALL_VALUES || pp.kind == P_ALL_INDICES) && pp.a != NONE) fixed[pp.a] = 0;
+      if (pp.kind == P_FILTER && pp.b != NONE) fixed[pp.b] = 0;
+    }
+    // the key run of each access clause's query: (var, key ids)
+    typedef std::vector<uint32_t> Run;
+    std::vector<std::pair<uint32_t, Run>> cand;   // query id, var followed by the run's key ids
+    for (auto& pc : clauses) {
+      if (pc.kind != C_ACCESS) continue;
+      const PQuery& q = queries[pc.a];
+      if (q.n < 2) continue;
+      const PPart& head = parts[q.first];
+      if (head.kind != P_VAR_HEAD || !head.c || !fixed[head.a]) continue;
+      Run r{head.a};
+      // the `[*]` the parser puts after a variable is skipped by the walker: the run starts behind it
+      uint32_t i = 1;
+      if (parts[q.first + 1].kind == P_ALL_INDICES) { if (parts[q.first + 1].a != NONE) continue; i = 2; }
+      for (; i < q.n && parts[q.first + i].kind == P_KEY && r.size() < 256; i++) r.push_back(parts[q.first + i].a);
+      if (r.size() > 1) cand.push_back({pc.a, r});
+    }
+    assign_prefix_slots(cand);
+  }
+
+  // Each candidate query takes the longest run (origin + keys) it shares with another candidate, and the slots go to
+  // the runs that save the most steps.  A query whose longest shared run is shared only with queries that took a
+  // longer one stays alone and gets no slot (`%a.Properties.Other.V` beside two `%a.Properties.Other.W`): the entry of the
+  // longer run holds the node at its end, which is of no use to the shorter one.
+  void assign_prefix_slots(const std::vector<std::pair<uint32_t, std::vector<uint32_t>>>& cand) {
+    typedef std::vector<uint32_t> Run;
+    std::map<Run, uint32_t> users;   // every prefix of every run -> queries that walk it
+    for (auto& cq : cand)
+      for (size_t len = 2; len <= cq.second.size(); len++) users[Run(cq.second.begin(), cq.second.begin() + len)]++;
+    std::map<Run, std::vector<uint32_t>> chosen;   // run -> the queries that take it
+    for (auto& cq : cand)
+      for (size_t len = cq.second.size(); len >= 2; len--) {
+        const Run r(cq.second.begin(), cq.second.begin() + len);
+        if (users[r] >= 2) { chosen[r].push_back(cq.first); break; }
+      }
+    std::vector<std::pair<uint32_t, Run>> order;   // steps saved, run
+    for (auto& ch : chosen)
+      if (ch.second.size() >= 2) order.push_back({(uint32_t)((ch.second.size() - 1) * (ch.first.size() - 1)), ch.first});
+    std::stable_sort(order.begin(), order.end(), [](const std::pair<uint32_t, Run>& x, const std::pair<uint32_t, Run>& y) { return x.first > y.first; });
+    for (size_t s = 0; s < order.size() && s < kPrefixSlots; s++)
+      for (uint32_t qid : chosen[order[s].second])
+        queries[qid].pad |= (uint32_t)(s + 1) << 8 | (uint32_t)(order[s].second.size() - 1) << 16;
+  }
+
   void assemble() {
     // a let's query is evaluated in its block's scope: its filters may lean on that block's lets
     std::vector<uint32_t> query_block(queries.size(), NONE);
@@ -697,7 +758,7 @@ struct Compiler {
           if (pp.b == NONE && quick_conj(pp.a)) pp.c |= 1u << 29;     // eval_core.inc QUICK_FILTER
         }
       }
-    // PQuery.pad = 1: a walk of the query does nothing but produce results -- no named `*` / `[*]` / filter
+    // PQuery.pad bit 0: a walk of the query does nothing but produce results -- no named `*` / `[*]` / filter
     // (captures into the root scope), no `%var` key, no map-key filter (its records join the clause's) -- so
     // the lanes of a document's group may split its first fan-out (eval_recursive.inc split_merge)
     for (size_t q = 0; q < queries.size(); q++) {
@@ -717,6 +778,7 @@ struct Compiler {
     for (auto& pc : clauses)
       if (pc.kind == C_BLOCK && blocks[pc.b].nlets == 0 && coop_conj(blocks[pc.b].conj, 0)) pc.c = 1;
     mark_root_vars();
+    mark_prefix_slots();
     std::vector<uint32_t> blob(sizeof(ProgHeader) / 4 + 2, 0);
     ProgHeader& h = P.hdr;
     put(blob, h.off_strs, h.n_strs, P.strs);

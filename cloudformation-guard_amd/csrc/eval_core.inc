@@ -71,6 +71,8 @@ struct WaveConst {
   uint32_t group;        // lanes per document (LaunchArgs::lane_group)
   uint32_t split_on;     // lane groups may split walks (LaunchArgs::lane_group bit 16 clear; GG_SPLIT_WALK=0 sets it)
   uint32_t sguard;       // LaunchArgs::stack_guard
+  uint32_t syn_off;      // heap offset of the synthetic-int table: the tile's first persist allocation, the same for
+                         // every tile of the launch (its word in the lane's Ctx went to the prefix memo's valid bits)
 };
 __shared__ WaveConst g_wave;
 #define C_HEAP(c) g_wave.heap
@@ -82,6 +84,7 @@ __shared__ WaveConst g_wave;
 #define C_TYPE_KEY(c) g_wave.type_key
 #define C_TIX(c) ((c).tix_off != NONE ? g_wave.tix + (c).tix_off : nullptr)
 #define C_SGUARD(c) g_wave.sguard
+#define C_SYN(c) g_wave.syn_off
 #else
 #define C_HEAP(c) (c).heap
 #define C_DN(c) (c).dn
@@ -92,6 +95,7 @@ __shared__ WaveConst g_wave;
 #define C_TYPE_KEY(c) (c).type_key
 #define C_TIX(c) (c).tix
 #define C_SGUARD(c) (c).sguard
+#define C_SYN(c) (c).syn_off
 #endif
 
 #if GG_CTX_PACK
@@ -126,7 +130,9 @@ struct Ctx {
   uint32_t memo;         // persist offset: u32 per name slot (3 = unknown)
   uint32_t split;        // lane groups: 1 + the walker level whose entries the group's lanes share out (0: none)
   uint32_t nsyn;         // synthetic ints (count()) in this tile
-  uint32_t syn_off;      // persist offset of synthetic table (16 B each: src, lo, hi, pad)
+#if !GG_LANE
+  uint32_t syn_off;      // persist offset of synthetic table (16 B each: src, lo, hi, pad); lane mode: g_wave.syn_off
+#endif
   uint32_t resmap;       // document-relative node of root.Resources, or NONE
   uint32_t ffok;         // node whose fast-filter test the enclosing fan-out already passed
   uint32_t wbase;        // persist offset of the query walker's level stack
@@ -141,6 +147,9 @@ struct Ctx {
   // An odd stride in words spreads them over all 64 banks (static_assert below).  The word is the lane's
   // output flag: with several lanes per document (LaunchArgs::lane_group) only the first writes records.
   uint32_t mute;
+  // prefix memo (walk_run_body<false>, one lane per tile): valid bit of entry (slot, j) at slot * PM_CAP + j,
+  // cleared with the tile.  It took syn_off's place, so the stride (and the kernel's LDS) is what it was.
+  uint32_t pm;
 #endif
 #ifdef GG_STATS
   uint32_t st[8];        // diagnostic counters (build variant "stats" only)
@@ -299,7 +308,7 @@ DEV uint32_t qkind(const QR& q) { return q.meta & 3u; }
 DEV DNode node(const LCtx& c, uint32_t ref) {
   STAT(c, 0);
   if (ref & SYN_BIT) {
-    const gU32* s = (const gU32*)haddr(c, c.syn_off + 16u * (ref & 0xFFFFu));
+    const gU32* s = (const gU32*)haddr(c, C_SYN(c) + 16u * (ref & 0xFFFFu));
     DNode d; d.kind = K_INT; d.count = 0; d.a = s[1]; d.b = s[2]; d.key_off = NONE; d.key_len = 0; d.key_hash = 0; d.parent = NONE;
     return d;
   }
@@ -629,7 +638,7 @@ DEV uint32_t aux_store(LCtx& c, const Rec& w) {
 // so the value goes to a side record instead: node = SYN_BIT | that record's index (reporter R::N).
 DEV QR publishable(LCtx& c, QR q) {
   if (q.meta != 0xFFFFFFFFu && (q.node & SYN_BIT) && q.node != NONE) {
-    const gU32* s = (const gU32*)haddr(c, c.syn_off + 16u * (q.node & 0xFFFFu));
+    const gU32* s = (const gU32*)haddr(c, C_SYN(c) + 16u * (q.node & 0xFFFFu));
     QR o; o.node = s[0]; o.meta = QR_SYNTH_INT; o.uref = s[1]; o.aux = s[2];
     if (qkind(q) != QR_UNRESOLVED) return o;
     Rec a; a.kind = REC_AUX; a.clause = NONE; a.x = 0; a.y = 0; a.from = o;
@@ -1423,9 +1432,36 @@ struct WState {
   uint32_t rb, st, voff, vn;                                  // frame argument; served results
 };
 
+// Prefix memo (one lane per tile).  Rules repeat a walk: consecutive clauses over `%buckets.Properties.
+// PublicAccessBlockConfiguration.<leaf>` redo the two key steps for every bucket.  The compiler gives the access
+// clauses' queries that share a run of plain key steps right after the same root-only `%var` head a slot (PQuery.pad
+// bits 8-15: slot + 1, bits 16-23: steps in the run; compiler.cpp mark_prefix_slots).  The first walk of value j
+// that passes the run's end stores the node it reached in entry (slot, j); later walks of value j descend from
+// there.  A plain key step on a map writes no record, captures nothing and leaves rec_created alone, so both walks
+// give the same results.  Only a run resolved by exact keys from converter state 0 is stored or reused (the
+// state at the run's end is then 0 again); a failed prefix is never stored, so it is walked again and yields
+// today's unresolved result.  The marked variables are root query / function lets nothing captures into: their
+// value list is fixed for the tile once resolved, so (slot, j) names one value.  Entries live in the lane heap
+// below the walker's level stack (PM_BYTES, allocated with the tile), one node reference each: a hit is one heap
+// read against one node read and one dependent entry scan per key step.  The valid bits are Ctx.pm, cleared with
+// the tile, so nothing of a previous tile is read.  Values at or past PM_CAP are walked as before.  The walker's
+// code generation decides whether this pays (DESIGN.md 4.1, round 7): the miss is one register kept across the
+// descent and a compare per step -- entries that carried the node's words, a second inlined key scan, a call or a
+// request to the driver for the miss all cost the other rules files more than the memo saved.
+// GG_PREFIX_MEMO=0 builds without it (A/B).
+#ifndef GG_PREFIX_MEMO
+#define GG_PREFIX_MEMO 1
+#endif
+static const uint32_t PM_CAP = kPrefixCap, PM_BYTES = kPrefixSlots * kPrefixCap * 4;   // guard_types.h
+static const uint32_t SYN_BYTES = 256 * 16;   // the synthetic-int table (256 of 16 B), a tile's first persist allocation
+#define GG_PM (GG_LANE && GG_PREFIX_MEMO)
+#if GG_PM
+DEV gU32* pm_entry(const LCtx& c, uint32_t bit) { return (gU32*)haddr(c, c.wbase - PM_BYTES + 4u * bit); }
+#endif
+
 // GROUP: the walker of lane groups (LaunchArgs::lane_group > 1), with the split-walk and shared-chunk hooks; a
 // separate instantiation, so the walker the one-lane-per-tile launches inline carries none of their registers
-// (walk_run's frame: 116 B without them, 188 B with)
+// (walk_run's frame: 124 B without them, 188 B with)
 template <bool GROUP>
 DEV uint32_t walk_run_body(LCtx& c, WState& w) { FCALL(c, 7);
   const PQuery Q = PG(c, queries)[w.qid];
@@ -1450,6 +1486,9 @@ DEV uint32_t walk_run_body(LCtx& c, WState& w) { FCALL(c, 7);
     Tcn = lcn;
     tdepth = (int32_t)d;
   };
+#if GG_PM
+  uint32_t pm = 0;       // a memo miss under way: (entry bit + 1) << 16 | the step after the run; 0 = none
+#endif
   switch (w.site) {
     case WS_START: break;
     case WS_VAR:
@@ -1492,6 +1531,16 @@ DEV uint32_t walk_run_body(LCtx& c, WState& w) { FCALL(c, 7);
     while (descend) {
       descend = false;
       if (c.err) break;
+#if GG_PM
+      if constexpr (!GROUP) {
+        // the run's end is reached only through its resolved key steps (a failed step ends the descent)
+        if (pm && qi == (pm & 0xFFFFu)) {
+          const uint32_t bit = (pm >> 16) - 1u;
+          if (!conv) { *pm_entry(c, bit) = cur; c.pm |= 1u << bit; }
+          pm = 0;
+        }
+      }
+#endif
       if (qi >= Q.n) { qr_push(c, mk_qr(cur, QR_RESOLVED)); break; }
       const PPart part = PG(c, parts)[Q.first + qi];
       uint32_t lkind = NONE, ln = 0;
@@ -1666,6 +1715,18 @@ DEV uint32_t walk_run_body(LCtx& c, WState& w) { FCALL(c, 7);
               L.fpushed = 1;
             }
             qi = index; cur = e.node; resolver = f; conv = L.conv;
+#if GG_PM
+            if constexpr (!GROUP) {
+              // the mark is read here, not kept with Q: a query without one pays an LDS read and a branch
+              pm = 0;
+              const uint32_t mark = PG(c, queries)[qid].pad >> 8, j = L.j0 - 1u;
+              if (mark && j < PM_CAP && !L.conv) {
+                const uint32_t bit = ((mark & 0xFFu) - 1u) * PM_CAP + j, end = index + (mark >> 8);
+                if ((c.pm >> bit) & 1u) { cur = *pm_entry(c, bit); qi = end; }
+                else pm = ((bit + 1u) << 16) | end;
+              }
+            }
+#endif
             got = true;
             break;
           }

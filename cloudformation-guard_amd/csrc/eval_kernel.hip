@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_LANE
     g_wave.heap = heap; g_wave.nodes = A.docs.nodes; g_wave.klen = A.docs.klen; g_wave.db = A.docs.bytes;
     g_wave.tix = A.docs.tix; g_wave.fcap = FRAMES_BYTES; g_wave.rcap = A.lane_recs_bytes; g_wave.type_key = A.docs.type_key;
     g_wave.recs = A.recs; g_wave.rchunk = A.rec_chunk; g_wave.sguard = A.stack_guard;
-    g_wave.rstride = L; g_wave.group = G; g_wave.split_on = (A.lane_group >> 16) ? 0u : 1u;
+    g_wave.syn_off = A.lane_heap_bytes - SYN_BYTES; g_wave.rstride = L; g_wave.group = G; g_wave.split_on = (A.lane_group >> 16) ? 0u : 1u;
   }
   __syncthreads();
   uint32_t staged = NONE;
@@ -225,8 +225,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GG_LANE
     c.mute = leader ? 0u : 1u;
     if (active) {
       tile_begin<true>(c, A, P, doc, heap, A.lane_heap_bytes, FRAMES_BYTES, A.lane_recs_bytes);
-      c.syn_off = alloc_pers(c, 256 * 16);
+      // two regions are addressed without an offset word in the Ctx: the synthetic-int table at g_wave.syn_off
+      // and the prefix-memo entries right below the level stack (eval_core.inc pm_entry).  An allocation that
+      // lands elsewhere (one inserted or reordered here) fails the tile with E_HEAP, which hands it to the wave
+      // kernel, instead of reading the wrong region.
+      const uint32_t syn_at = alloc_pers(c, SYN_BYTES);
       c.wbase = alloc_pers(c, WLEVELS * (uint32_t)sizeof(WLevel)); c.wdepth = 0;
+      const uint32_t pm_at = alloc_pers(c, PM_BYTES);
+      if (!c.err && (syn_at != g_wave.syn_off || pm_at + PM_BYTES != c.wbase)) fail(c, E_HEAP);
+      c.pm = 0;
       c.memo = alloc_pers(c, (P->n_slots ? P->n_slots : 1) * 4);
       if (!c.err) for (uint32_t i = 0; i < P->n_slots; i++) u32a(c, c.memo)[i] = 3u;
       c.vtab = alloc_pers(c, (P->n_vars ? P->n_vars : 1) * 16);

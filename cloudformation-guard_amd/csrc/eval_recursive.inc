@@ -179,12 +179,12 @@ DEVN uint32_t walk_run_group(LCtx& c, WState& w) { return walk_run_body<true>(c,
 #if GG_LANE
 // Split walks: the lanes of a document's group (LaunchArgs::lane_group) walk the entries of a top-level query's
 // first fan-out level round robin (eval_core.inc split_skip) and merge their result lists in entry order, so each
-// lane leaves with the list the sequential walk gives.  Only a query the compiler marked (PQuery.pad: no
+// lane leaves with the list the sequential walk gives.  Only a query the compiler marked (PQuery.pad bit 0: no
 // captures, `%var` keys or map-key filters -- nothing a walk does besides producing results) and a group that is
 // all here; a walk whose entries recorded anything (a filter over a scalar), raised an error or counted ran out
 // of room is redone in full by every lane, so records and errors come in the reference's order.
 DEV bool split_start(const LCtx& c, uint32_t qid) {
-  if (g_wave.group < 2u || !g_wave.split_on || c.split || !PG(c, queries)[qid].pad) return false;
+  if (g_wave.group < 2u || !g_wave.split_on || c.split || !(PG(c, queries)[qid].pad & 1u)) return false;
   const uint32_t G = g_wave.group, gbase = __lane_id() & ~(G - 1u);
   const uint64_t gmask = (G >= 64u ? ~0ull : ((1ull << G) - 1ull)) << gbase;
   return (__ballot(1) & gmask) == gmask;
@@ -764,7 +764,7 @@ DEVN View resolve_function(LCtx& c, uint32_t fid, uint32_t frame) { FCALL(c, 10)
   uint32_t src = NONE;
   if (arg.n) src = qra(c, arg.off)->node;
   if (c.nsyn >= 256) { fail(c, E_HEAP); return out; }
-  gU32* s = (gU32*)haddr(c, c.syn_off + 16u * c.nsyn);
+  gU32* s = (gU32*)haddr(c, C_SYN(c) + 16u * c.nsyn);
   s[0] = src; s[1] = cnt; s[2] = 0; s[3] = 0;
   uint32_t ref = SYN_BIT | c.nsyn++;
   out.off = alloc_tmp(c, 16); out.n = 1;

@@ -74,7 +74,14 @@ struct PPart {
   uint32_t c;
 };
 
+// PQuery.pad, packed by the compiler (compiler.cpp assemble):
+//   bit 0       the walk only produces results, so a lane group may split its first fan-out (split_start)
+//   bits 8-15   prefix-memo slot + 1, 0 = none (mark_prefix_slots; eval_core.inc "Prefix memo")
+//   bits 16-23  plain key steps in the memoized run
 struct PQuery { uint32_t first, n, match_all, pad; };
+// prefix memo: slots per rules file and values of a variable held per slot; one valid bit each in a Ctx word
+static const uint32_t kPrefixSlots = 2, kPrefixCap = 16;
+static_assert(kPrefixSlots * kPrefixCap <= 32, "the prefix memo's valid bits are one 32-bit word");
 
 enum ClauseKind : uint32_t {
   C_ACCESS = 0, C_NAMED = 1, C_BLOCK = 2, C_WHEN = 3, C_TYPEBLOCK = 4, C_PARAM = 5,

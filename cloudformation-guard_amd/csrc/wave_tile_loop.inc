@@ -20,7 +20,7 @@
     uint32_t doc = tile / A.nfiles, file = tile % A.nfiles;
     if (file != staged) { P = stage_program(&A.progs[file], &s_prog, s_blob, A.lds_prog_words); staged = file; }
     tile_begin<false>(c, A, P, doc, heap, A.heap_bytes, A.wave_frames_bytes, A.wave_recs_bytes);
-    c.syn_off = alloc_pers(c, 256 * 16);
+    c.syn_off = alloc_pers(c, SYN_BYTES);
     c.wbase = alloc_pers(c, WLEVELS * (uint32_t)sizeof(WLevel)); c.wdepth = 0;
     c.memo = alloc_pers(c, (P->n_slots ? P->n_slots : 1) * 4);
     if (!c.err) for (uint32_t i = 0; i < P->n_slots; i++) u32a(c, c.memo)[i] = 3u;
