@@ -431,6 +431,7 @@ struct gg_session {
   uint32_t max_top = 1;
   uint32_t nslots = 0;            // wave-mode grid
   uint32_t lane_slots = 0;        // lane-mode grid (waves)
+  uint64_t coop_docs = 0;         // the last device load: documents parsed by the cooperative kernels
   uint32_t lane_docs = 64;        // lane mode: documents per batch (session_upload)
   uint32_t lane_group = 1;        // lane mode: lanes per document (64 / lane_docs in lane groups, else 1)
   uint32_t heap_bytes = 512 * 1024;
@@ -4216,17 +4217,22 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
     std::string why;
     if (!ensure_device(why, s->device, &s->device)) { set_err(err, -1, why); return -1; }
     if (s->docs.ndocs()) { set_err(err, 18, "IllegalArguments: the device loader fills an empty session"); return -1; }
-    // the device parse is one lane per document: a batch of few, large documents (Terraform plans of
-    // thousands of resources) leaves the device nearly idle -- 2048 plans parsed at 0.3 GB/s of text
-    // (profiles/r04a_bench_cfg4_lane_2048.json) against ~1 GB/s on 16 host threads -- so such a batch is
-    // refused as a whole and the caller loads it on host threads (GG_JSON_FEW_DOCS=0 keeps it on the device)
+    // the lane passes give a document to one lane: a batch of few, large documents (Terraform plans of
+    // thousands of resources) leaves the device nearly idle there -- 2048 plans parsed at 0.3 GB/s of text
+    // (profiles/r04a_bench_cfg4_lane_2048.json) against ~1 GB/s on 16 host threads.  Large JSON documents
+    // go to the cooperative kernels, a workgroup each (json_coop.inc); when what is left for the lanes is
+    // still few and large (YAML plans), the batch is refused as a whole and the caller loads it on host
+    // threads (GG_JSON_FEW_DOCS=0 keeps it on the device)
     {
       uint64_t total = 0;
-      for (size_t i = 0; i < n; i++) total += lens[i];
+      size_t nl = 0;
+      const uint64_t coop_min = gpu_json_coop_min();
+      for (size_t i = 0; i < n; i++)
+        if (!gpu_json_coop_doc(texts[i], lens[i], coop_min)) { total += lens[i]; nl++; }
       const bool force = getenv("GG_JSON_FEW_DOCS") && atoi(getenv("GG_JSON_FEW_DOCS")) == 0;
-      if (!force && n < (size_t)dev_ncu(s->device) * 64 && n && total / n > (64u << 10)) {
-        set_note(err, "too few documents for the lane-per-document device parse (" + std::to_string(n) + " documents of " +
-                          std::to_string(total / n) + " bytes on average): load them on host threads");
+      if (!force && nl < (size_t)dev_ncu(s->device) * 64 && nl && total / nl > (64u << 10)) {
+        set_note(err, "too few documents for the lane-per-document device parse (" + std::to_string(nl) + " documents of " +
+                          std::to_string(total / nl) + " bytes on average): load them on host threads");
         return 1;
       }
     }
@@ -4293,6 +4299,7 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
     dev_nodes = nullptr;
     s->resident = res;
     res = ResidentArena{};
+    s->coop_docs = st.coop_docs;
     load_stats(st, stats);
     if (getenv("GG_LOAD_TRACE"))
       fprintf(stderr, "[load] session holds the batch %8.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl).count());
@@ -4530,6 +4537,7 @@ int64_t gg_session_stat(gg_session* s, int32_t what) {
     case 21: return (int64_t)s->parse_errors.size();   // rules files that did not parse (exit code 5)
     case 22: return (int64_t)s->lane_group;   // lanes per document of the lane kernel (1: one lane per tile)
     case 23: return (int64_t)s->lane_docs;    // documents per lane batch
+    case 24: return (int64_t)s->coop_docs;    // documents the last device load parsed a workgroup each
     default: return -1;
   }
 }

@@ -1,5 +1,5 @@
 // GPU document loader: strict-JSON documents -> the columnar node arena,
-// parsed on the MI355X.  Produces exactly the arena the host JSON fast path builds
+// parsed on the MI355X: a lane per document, or a workgroup per document for large ones.  Produces exactly the arena the host JSON fast path builds
 // (doc_loader.cpp load_json_fast: same node layout, marks and scalar typing), with string ids
 // interned batch-wide on the device.  Replaces, for JSON input, the reference's
 // Loader::load + PathAwareValue::try_from (guard/src/rules/libyaml/loader.rs:31-195,
@@ -20,7 +20,14 @@ struct GpuLoadStats {
   uint64_t text_bytes = 0, nodes = 0, distinct_strings = 0, pool_bytes = 0;
   uint32_t table_retries = 0;   // intern-table doublings
   uint64_t refused_docs = 0;    // documents outside the device subset, built by the host loader
+  uint64_t coop_docs = 0;       // documents the cooperative kernels parsed (a workgroup per document)
 };
+
+// Routing: a document that opens with { or [ after leading whitespace and holds at least `coop_min` bytes
+// is parsed by a workgroup (json_coop.inc) instead of a lane.  gpu_json_coop_min() is GG_JSON_COOP_MIN
+// (default 65536; 0 sends every JSON document that way).
+uint64_t gpu_json_coop_min();
+bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min);
 
 // Appends `n` documents (texts[i] of lens[i] bytes, named names[i]) to the EMPTY batch `out`.
 // A document outside the subset the device parser proves identical to the host loader (libyaml-only

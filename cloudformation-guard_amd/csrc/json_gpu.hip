@@ -19,6 +19,9 @@
 //                 bytes compared with its id's pool bytes, so a fingerprint collision cannot merge
 //                 two strings silently, and every map key against its earlier siblings (duplicate
 //                 keys); either refuses the document.
+// A large JSON document (GG_JSON_COOP_MIN bytes, default 65536) is given to a workgroup instead: the
+// cooperative kernels (json_coop.inc) stand in for passes 1 and 2 and leave the same outputs, the lane
+// passes skip it, passes 3 and 4 take both.
 // A document outside the subset is refused on its own (per-document flag): the passes skip it, the
 // host loader builds it (doc_loader.cpp, the libyaml path) and its nodes join the batch at the
 // document's position, so results never depend on which loader ran.  Only batch-wide limits (string
@@ -74,6 +77,9 @@ struct NodeRec {
 };
 static_assert(sizeof(NodeRec) == 64, "one 64-byte record per node");
 
+struct Tok;      // the cooperative parse's tokens (json_coop.inc)
+struct TokAux;
+
 struct JArgs {
   const uint8_t* text;          // all documents, 16 zero bytes of padding at the end
   const uint64_t* off;          // [ndocs + 1]
@@ -105,6 +111,14 @@ struct JArgs {
   uint32_t* doc_bad;            // per document: its refusal reason (BAD_*), 0 = loaded on the device
   uint8_t* is_yaml;             // per document: parsed by the YAML passes
   uint32_t* bad_at;             // diagnostics (GG_LOAD_DIAG): the YAML passes' byte offset of a refusal
+  // the cooperative parse (json_coop.inc): a workgroup per flagged document
+  const uint8_t* is_coop;       // per document: parsed by the cooperative kernels (the lane passes skip it)
+  const uint32_t* coop_list;    // the flagged documents
+  uint32_t ncoop;
+  uint32_t* n_tok;              // per document: its token count (index kernel, count instantiation)
+  const uint64_t* tok_base;     // per document: its first token
+  Tok* toks;
+  TokAux* aux;
 };
 
 __device__ inline void refuse(const JArgs& A, uint32_t why) { atomicCAS(A.bad, 0u, why); }
@@ -380,6 +394,40 @@ __device__ uint32_t intern_slot(const JArgs& A, uint64_t key, uint32_t len, uint
   return ~0u;
 }
 
+// A string occurrence whose opening quote is at i: returns the index after it, 0 on refusal; EMIT -> its
+// intern table slot and decoded length.  Shared by the lane passes and the cooperative emit (json_coop.inc).
+template <bool EMIT>
+__device__ __attribute__((always_inline)) uint64_t string_occurrence(const JArgs& A, Text& T, uint64_t i, uint32_t d, uint32_t& cont,
+                                                                     uint32_t* slot_out, uint32_t* len_out) {
+  Fp fp;
+  // fingerprint of the decoded bytes, 4 at a time (the device table's own key: nothing outside
+  // this loader compares it)
+  struct HashSink {
+    WordStream ws;
+    uint64_t h;
+    __device__ void byte(uint32_t c) { ws.byte(c, [&](uint32_t w, uint32_t) { h = (h ^ w) * 0x100000001b3ull; }); }
+    __device__ void run(const Text& T, uint32_t k, uint32_t r) {
+      ws.run(T, k, r, [&](uint32_t w, uint32_t) { h = (h ^ w) * 0x100000001b3ull; });
+    }
+  } hs{WordStream(), fp.h};
+  const uint64_t end = decode_string<EMIT>(T, i, hs, cont);
+  if (!end) return 0;
+  fp.h = (hs.h ^ hs.ws.word) * 0x100000001b3ull;
+  fp.len = hs.ws.len;
+  if (EMIT) {
+    const uint64_t key64 = (mix64(fp.h ^ ((uint64_t)fp.len * 0x9E3779B97F4A7C15ull)) & A.fp_mask) | 1ull;
+#if GG_JDIAG_NOINTERN
+    const uint32_t s = (uint32_t)key64 & 1023u;
+#else
+    const uint32_t s = intern_slot(A, key64, fp.len, d, (uint32_t)i);
+#endif
+    if (s == ~0u) { refuse(A, BAD_TABLE); return 0; }
+    *slot_out = s;
+    *len_out = fp.len;
+  }
+  return end;
+}
+
 struct Frame {
   uint32_t first;   // EMIT / VERIFY: first child (document-relative)
   uint32_t j;       // elements done
@@ -408,6 +456,7 @@ __device__ void parse_doc(const JArgs& A, uint32_t d) {
   auto bad = [&](uint32_t why) { if (!A.doc_bad[d]) A.doc_bad[d] = why; };   // the first reason
   if (MODE == M_COUNT) { A.n_nodes[d] = 0; A.n_cont[d] = 0; A.n_str[d] = 0; }
   else if (A.doc_bad[d] || A.is_yaml[d]) return;
+  if (A.is_coop[d]) return;   // the cooperative kernels parse it
   const uint64_t nb = (MODE >= M_EMIT) ? A.node_base[d] : 0;
   const uint64_t cb = b0 >> 1;
   uint32_t nn = 1, nc = 0, ns = 0, ci = 0, next = 1;
@@ -417,37 +466,9 @@ __device__ void parse_doc(const JArgs& A, uint32_t d) {
   Frame top{};
   uint32_t sp = 0;
 
-  // a string occurrence at i (the opening quote): returns the index after it, 0 on refusal;
-  // EMIT -> its intern table slot and decoded length
+  // a string occurrence at i (the opening quote)
   auto string_at = [&](uint32_t* slot_out, uint32_t* len_out) -> uint64_t {
-    Fp fp;
-    uint64_t end;
-    // fingerprint of the decoded bytes, 4 at a time (the device table's own key: nothing outside
-    // this loader compares it)
-    struct HashSink {
-      WordStream ws;
-      uint64_t h;
-      __device__ void byte(uint32_t c) { ws.byte(c, [&](uint32_t w, uint32_t) { h = (h ^ w) * 0x100000001b3ull; }); }
-      __device__ void run(const Text& T, uint32_t k, uint32_t r) {
-        ws.run(T, k, r, [&](uint32_t w, uint32_t) { h = (h ^ w) * 0x100000001b3ull; });
-      }
-    } hs{WordStream(), fp.h};
-    end = decode_string<MODE == M_EMIT>(T, i, hs, cont);
-    if (!end) return 0;
-    fp.h = (hs.h ^ hs.ws.word) * 0x100000001b3ull;
-    fp.len = hs.ws.len;
-    if (MODE == M_EMIT) {
-      const uint64_t key64 = (mix64(fp.h ^ ((uint64_t)fp.len * 0x9E3779B97F4A7C15ull)) & A.fp_mask) | 1ull;
-#if GG_JDIAG_NOINTERN
-      const uint32_t s = (uint32_t)key64 & 1023u;
-#else
-      const uint32_t s = intern_slot(A, key64, fp.len, d, (uint32_t)i);
-#endif
-      if (s == ~0u) { refuse(A, BAD_TABLE); return 0; }
-      *slot_out = s;
-      *len_out = fp.len;
-    }
-    return end;
+    return string_occurrence<MODE == M_EMIT>(A, T, i, d, cont, slot_out, len_out);
   };
 
   // EMIT: the element being emitted -- its key (table slot and length; NONE: no key), the key's
@@ -582,6 +603,7 @@ __device__ void parse_doc(const JArgs& A, uint32_t d) {
 }
 
 #include "yaml_gpu.inc"
+#include "json_coop.inc"
 
 // resident waves per SIMD the passes are compiled for (their VGPR budget: 512 / waves)
 #ifndef GG_JSON_WPE_COUNT
@@ -839,6 +861,18 @@ __global__ void __launch_bounds__(256) root_resources_kernel(const DNode* nodes,
   }
 }
 
+uint64_t gpu_json_coop_min() {
+  if (const char* e = getenv("GG_JSON_COOP_MIN")) return strtoull(e, nullptr, 0);
+  return 65536;
+}
+
+bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min) {
+  if (len < coop_min) return false;
+  size_t i = 0;
+  while (i < len && (text[i] == ' ' || text[i] == '\n')) i++;   // the lane parser's whitespace
+  return i < len && (text[i] == '{' || text[i] == '[');
+}
+
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused,
                    void** keep_nodes, ResidentArena* resident, ParamMerge* merge) {
@@ -915,6 +949,27 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   A.n_nodes = d_nn.p; A.n_cont = d_nc.p; A.n_str = d_ns.p; A.bad = d_bad.p; A.doc_bad = d_doc_bad.p; A.is_yaml = d_yaml.p; A.bad_at = diag ? d_bad_at.p : nullptr;
   DevArr<uint16_t> d_counts; d_counts.alloc(total / 2 + 1);
   A.counts = d_counts.p;
+  // large JSON documents go to the cooperative kernels (json_coop.inc), a workgroup each
+  const uint64_t coop_min = gpu_json_coop_min();
+  std::vector<uint8_t> coop(n, 0);
+  std::vector<uint32_t> coop_list;
+  for (size_t k = 0; k < n; k++)
+    if (gpu_json_coop_doc(texts[k], lens[k], coop_min)) { coop[k] = 1; coop_list.push_back((uint32_t)k); }
+  const uint32_t ncoop = (uint32_t)coop_list.size();
+  DevArr<uint8_t> d_coop; d_coop.alloc(n);
+  DevArr<uint32_t> d_coop_list, d_ntok;
+  DevArr<uint64_t> d_tokbase;
+  DevArr<Tok> d_toks;
+  DevArr<TokAux> d_aux;
+  JCHK(hipMemcpy(d_coop.p, coop.data(), n, hipMemcpyHostToDevice));
+  A.is_coop = d_coop.p; A.ncoop = ncoop;
+  if (ncoop) {
+    d_coop_list.alloc(ncoop); d_ntok.alloc(n); d_tokbase.alloc(n);
+    JCHK(hipMemcpy(d_coop_list.p, coop_list.data(), ncoop * 4ull, hipMemcpyHostToDevice));
+    JCHK(hipMemset(d_ntok.p, 0, n * 4));
+    A.coop_list = d_coop_list.p; A.n_tok = d_ntok.p; A.tok_base = d_tokbase.p;
+  }
+  const uint32_t cgrid = std::min<uint32_t>(std::max(ncoop, 1u), 65536u);
   const uint32_t dgrid = grid_for(n, 256);
   float ms_total = 0, ms = 0;
   auto bad_now = [&]() {
@@ -936,6 +991,32 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   JCHK(hipEventSynchronize(e1));
   JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
   mark("count pass");
+  if (ncoop) {
+    // the cooperative count: the index kernel sizes every flagged document's token buffer, then writes the
+    // tokens, and the tree kernel leaves what the lane count pass leaves (n_nodes, n_cont, n_str, counts)
+    JCHK(hipEventRecord(e0));
+    hipLaunchKernelGGL(json_coop_index_kernel<false>, dim3(cgrid), dim3(256), 0, 0, A);
+    JCHK(hipGetLastError());
+    JCHK(hipEventRecord(e1));
+    JCHK(hipEventSynchronize(e1));
+    JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
+    std::vector<uint32_t> ntok(n);
+    JCHK(hipMemcpy(ntok.data(), d_ntok.p, n * 4, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> tbase(n, 0);
+    uint64_t ntoks = 0;
+    for (uint32_t k : coop_list) { tbase[k] = ntoks; ntoks += ntok[k]; }
+    JCHK(hipMemcpy(d_tokbase.p, tbase.data(), n * 8, hipMemcpyHostToDevice));
+    d_toks.alloc(ntoks); d_aux.alloc(ntoks);
+    A.toks = d_toks.p; A.aux = d_aux.p;
+    JCHK(hipEventRecord(e0));
+    hipLaunchKernelGGL(json_coop_index_kernel<true>, dim3(cgrid), dim3(256), 0, 0, A);
+    hipLaunchKernelGGL(json_coop_tree_kernel, dim3(cgrid), dim3(256), 0, 0, A);
+    JCHK(hipGetLastError());
+    JCHK(hipEventRecord(e1));
+    JCHK(hipEventSynchronize(e1));
+    JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
+    mark("cooperative index + tree");
+  }
   if (bad_now()) return false;
   // the count pass's per-document refusals; a table / pool retry starts again from them
   JCHK(hipMemcpy(d_doc_bad0.p, d_doc_bad.p, n * 4, hipMemcpyDeviceToDevice));
@@ -1018,6 +1099,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     JCHK(hipEventRecord(e0));
     hipLaunchKernelGGL(json_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (yaml_on) hipLaunchKernelGGL(yaml_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
+    if (ncoop) hipLaunchKernelGGL(json_coop_emit_kernel, dim3(cgrid), dim3(256), 0, 0, A);
 #if !GG_JDIAG_NOINTERN
     hipLaunchKernelGGL(json_own_kernel, dim3(grid_for(tslots, 256)), dim3(256), 0, 0, A);
     hipLaunchKernelGGL(json_fix_verify_kernel, dim3(grid_for(n * 64ull, 256)), dim3(256), 0, 0, A);
@@ -1076,6 +1158,8 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     refused->push_back((uint32_t)k);
   }
   st.refused_docs = refused ? refused->size() : 0;
+  st.coop_docs = 0;
+  for (uint32_t k : coop_list) st.coop_docs += doc_bad[k] == 0;
   mark("doc_bad");
 
   // results to the host batch (the host keeps the reporter's columns and the intern index)
