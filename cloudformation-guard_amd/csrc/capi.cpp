@@ -1975,7 +1975,8 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
 // The batch entries load a batch of at least GG_BATCH_DEVICE_LOAD_MIN documents (64; 0 = never) with the
 // device loader (JSON and block-style YAML on the MI355X, the rest on host threads at their positions; input
 // parameters -- `params`, or the session's -- merged there too); when that path does not take the whole batch
-// -- too few large documents, a document the host loader then rejects, a parameter merge that fails -- the
+// -- too few large documents for the lanes that the cooperative kernels do not take (large YAML with
+// GG_YAML_COOP=0), a document the host loader then rejects, a parameter merge that fails -- the
 // documents load one by one on the host as before, so an error is still the first failing document's, with
 // the reference's message and precedence.
 static bool batch_device_load(gg_session* s, const validate_input_t* docs, size_t n_docs, size_t first, size_t count,
@@ -4219,16 +4220,18 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
     if (s->docs.ndocs()) { set_err(err, 18, "IllegalArguments: the device loader fills an empty session"); return -1; }
     // the lane passes give a document to one lane: a batch of few, large documents (Terraform plans of
     // thousands of resources) leaves the device nearly idle there -- 2048 plans parsed at 0.3 GB/s of text
-    // (profiles/r04a_bench_cfg4_lane_2048.json) against ~1 GB/s on 16 host threads.  Large JSON documents
-    // go to the cooperative kernels, a workgroup each (json_coop.inc); when what is left for the lanes is
-    // still few and large (YAML plans), the batch is refused as a whole and the caller loads it on host
-    // threads (GG_JSON_FEW_DOCS=0 keeps it on the device)
+    // (profiles/r04a_bench_cfg4_lane_2048.json) against ~1 GB/s on 16 host threads.  Large documents go to
+    // the cooperative kernels (json_coop.inc, and unless GG_YAML_COOP=0 yaml_coop.inc for block YAML;
+    // gpu_json_coop_doc decides, here as in the loader); when what is left for the lanes is still few and
+    // large, the batch is refused as a whole and the caller loads it on host threads (GG_JSON_FEW_DOCS=0
+    // keeps it on the device)
     {
       uint64_t total = 0;
       size_t nl = 0;
       const uint64_t coop_min = gpu_json_coop_min();
+      const bool yaml_coop = gpu_yaml_coop_on();
       for (size_t i = 0; i < n; i++)
-        if (!gpu_json_coop_doc(texts[i], lens[i], coop_min)) { total += lens[i]; nl++; }
+        if (!gpu_json_coop_doc(texts[i], lens[i], coop_min, yaml_coop)) { total += lens[i]; nl++; }
       const bool force = getenv("GG_JSON_FEW_DOCS") && atoi(getenv("GG_JSON_FEW_DOCS")) == 0;
       if (!force && nl < (size_t)dev_ncu(s->device) * 64 && nl && total / nl > (64u << 10)) {
         set_note(err, "too few documents for the lane-per-document device parse (" + std::to_string(nl) + " documents of " +

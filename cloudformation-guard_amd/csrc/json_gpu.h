@@ -23,11 +23,15 @@ struct GpuLoadStats {
   uint64_t coop_docs = 0;       // documents the cooperative kernels parsed (a workgroup per document)
 };
 
-// Routing: a document that opens with { or [ after leading whitespace and holds at least `coop_min` bytes
-// is parsed by a workgroup (json_coop.inc) instead of a lane.  gpu_json_coop_min() is GG_JSON_COOP_MIN
-// (default 65536; 0 sends every JSON document that way).
+// Routing: a document of at least `coop_min` bytes is parsed cooperatively instead of by one lane: one that
+// opens with { or [ after leading whitespace by a workgroup (json_coop.inc), any other one -- block-style
+// YAML -- by a workgroup's line index and a lane per segment (yaml_coop.inc; *yaml is set then).
+// gpu_json_coop_min() is GG_JSON_COOP_MIN (default 65536; 0 sends every document that way), the one
+// threshold for both formats.  GG_YAML_COOP=0|1 turns only the YAML path off or on; GG_YAML_DEVICE=0 turns
+// every YAML path off; gpu_yaml_coop_on() reads the two switches, once per load.
 uint64_t gpu_json_coop_min();
-bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min);
+bool gpu_yaml_coop_on();
+bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min, bool yaml_coop, bool* yaml = nullptr);
 
 // Appends `n` documents (texts[i] of lens[i] bytes, named names[i]) to the EMPTY batch `out`.
 // A document outside the subset the device parser proves identical to the host loader (libyaml-only

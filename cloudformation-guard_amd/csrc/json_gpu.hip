@@ -79,6 +79,8 @@ static_assert(sizeof(NodeRec) == 64, "one 64-byte record per node");
 
 struct Tok;      // the cooperative parse's tokens (json_coop.inc)
 struct TokAux;
+struct YLine;    // the cooperative YAML parse's line records and segments (yaml_coop.inc, yaml_gpu.inc)
+struct YSeg;
 
 struct JArgs {
   const uint8_t* text;          // all documents, 16 zero bytes of padding at the end
@@ -119,6 +121,16 @@ struct JArgs {
   const uint64_t* tok_base;     // per document: its first token
   Tok* toks;
   TokAux* aux;
+  // the cooperative YAML parse (yaml_coop.inc): n_tok / tok_base hold a flagged YAML document's line count
+  // and first line record
+  const uint32_t* ycoop_list;   // the flagged YAML documents
+  uint32_t nycoop;
+  YLine* ylines;                // one record per line
+  uint32_t* n_seg;              // per document: its segment count (segmentation kernel, count instantiation)
+  const uint64_t* seg_base;     // per document: its first segment
+  YSeg* ysegs;
+  uint64_t nsegs;               // all flagged documents' segments
+  uint16_t* ycnt;               // the segments' count pass: child counts in segment order (laid out as counts)
 };
 
 __device__ inline void refuse(const JArgs& A, uint32_t why) { atomicCAS(A.bad, 0u, why); }
@@ -604,6 +616,7 @@ __device__ void parse_doc(const JArgs& A, uint32_t d) {
 
 #include "yaml_gpu.inc"
 #include "json_coop.inc"
+#include "yaml_coop.inc"
 
 // resident waves per SIMD the passes are compiled for (their VGPR budget: 512 / waves)
 #ifndef GG_JSON_WPE_COUNT
@@ -866,11 +879,27 @@ uint64_t gpu_json_coop_min() {
   return 65536;
 }
 
-bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min) {
+// GG_YAML_COOP unset: on.  2048 templates of 71 KB load and upload in 0.238-0.246 s on the device against
+// 0.270-0.296 s on 16 host threads, three alternating runs each (profiles/yaml_coop_loader_measure.txt)
+static const bool kYamlCoopDefault = true;
+static bool env_on(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : dflt;
+}
+
+bool gpu_yaml_coop_on() { return env_on("GG_YAML_DEVICE", true) && env_on("GG_YAML_COOP", kYamlCoopDefault); }
+
+bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min, bool yaml_coop, bool* yaml) {
+  if (yaml) *yaml = false;
   if (len < coop_min) return false;
   size_t i = 0;
   while (i < len && (text[i] == ' ' || text[i] == '\n')) i++;   // the lane parser's whitespace
-  return i < len && (text[i] == '{' || text[i] == '[');
+  if (i >= len) return false;
+  if (text[i] == '{' || text[i] == '[') return true;
+  // what the JSON count pass hands to the YAML passes (BAD_NOTJSON)
+  if (!yaml_coop) return false;
+  if (yaml) *yaml = true;
+  return true;
 }
 
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
@@ -952,25 +981,46 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   // large JSON documents go to the cooperative kernels (json_coop.inc), a workgroup each
   const uint64_t coop_min = gpu_json_coop_min();
   std::vector<uint8_t> coop(n, 0);
-  std::vector<uint32_t> coop_list;
-  for (size_t k = 0; k < n; k++)
-    if (gpu_json_coop_doc(texts[k], lens[k], coop_min)) { coop[k] = 1; coop_list.push_back((uint32_t)k); }
-  const uint32_t ncoop = (uint32_t)coop_list.size();
+  // and large YAML documents to theirs (yaml_coop.inc)
+  std::vector<uint32_t> coop_list, ycoop_list;
+  const bool yaml_coop = gpu_yaml_coop_on();
+  for (size_t k = 0; k < n; k++) {
+    bool y = false;
+    if (!gpu_json_coop_doc(texts[k], lens[k], coop_min, yaml_coop, &y)) continue;
+    coop[k] = 1;
+    (y ? ycoop_list : coop_list).push_back((uint32_t)k);
+  }
+  const uint32_t ncoop = (uint32_t)coop_list.size(), nycoop = (uint32_t)ycoop_list.size();
   DevArr<uint8_t> d_coop; d_coop.alloc(n);
-  DevArr<uint32_t> d_coop_list, d_ntok;
-  DevArr<uint64_t> d_tokbase;
+  DevArr<uint32_t> d_coop_list, d_ycoop_list, d_ntok, d_nseg;
+  DevArr<uint64_t> d_tokbase, d_segbase;
   DevArr<Tok> d_toks;
   DevArr<TokAux> d_aux;
+  DevArr<YLine> d_ylines;
+  DevArr<YSeg> d_ysegs;
+  DevArr<uint16_t> d_ycnt;
   JCHK(hipMemcpy(d_coop.p, coop.data(), n, hipMemcpyHostToDevice));
-  A.is_coop = d_coop.p; A.ncoop = ncoop;
-  if (ncoop) {
-    d_coop_list.alloc(ncoop); d_ntok.alloc(n); d_tokbase.alloc(n);
-    JCHK(hipMemcpy(d_coop_list.p, coop_list.data(), ncoop * 4ull, hipMemcpyHostToDevice));
+  A.is_coop = d_coop.p; A.ncoop = ncoop; A.nycoop = nycoop;
+  if (ncoop || nycoop) {
+    d_ntok.alloc(n); d_tokbase.alloc(n);
     JCHK(hipMemset(d_ntok.p, 0, n * 4));
-    A.coop_list = d_coop_list.p; A.n_tok = d_ntok.p; A.tok_base = d_tokbase.p;
+    A.n_tok = d_ntok.p; A.tok_base = d_tokbase.p;
+  }
+  if (ncoop) {
+    d_coop_list.alloc(ncoop);
+    JCHK(hipMemcpy(d_coop_list.p, coop_list.data(), ncoop * 4ull, hipMemcpyHostToDevice));
+    A.coop_list = d_coop_list.p;
+  }
+  if (nycoop) {
+    d_ycoop_list.alloc(nycoop); d_nseg.alloc(n); d_segbase.alloc(n); d_ycnt.alloc(total / 2 + 1);
+    JCHK(hipMemcpy(d_ycoop_list.p, ycoop_list.data(), nycoop * 4ull, hipMemcpyHostToDevice));
+    JCHK(hipMemset(d_nseg.p, 0, n * 4));
+    A.ycoop_list = d_ycoop_list.p; A.n_seg = d_nseg.p; A.seg_base = d_segbase.p; A.ycnt = d_ycnt.p;
   }
   const uint32_t cgrid = std::min<uint32_t>(std::max(ncoop, 1u), 65536u);
+  const uint32_t ygrid = std::min<uint32_t>(std::max(nycoop, 1u), 65536u);
   const uint32_t dgrid = grid_for(n, 256);
+  uint32_t sgrid = 1;   // a lane per YAML segment
   float ms_total = 0, ms = 0;
   auto bad_now = [&]() {
     uint32_t b = 0;
@@ -991,11 +1041,14 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   JCHK(hipEventSynchronize(e1));
   JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
   mark("count pass");
-  if (ncoop) {
-    // the cooperative count: the index kernel sizes every flagged document's token buffer, then writes the
-    // tokens, and the tree kernel leaves what the lane count pass leaves (n_nodes, n_cont, n_str, counts)
+  if (ncoop || nycoop) {
+    // the cooperative count.  JSON: the index kernel sizes every flagged document's token buffer, then writes
+    // the tokens, and the tree kernel leaves what the lane count pass leaves (n_nodes, n_cont, n_str, counts).
+    // YAML: the index kernel sizes and writes the line records, the segmentation kernel sizes and writes the
+    // segments, and the segments' count pass and the fix kernel leave the same
     JCHK(hipEventRecord(e0));
-    hipLaunchKernelGGL(json_coop_index_kernel<false>, dim3(cgrid), dim3(256), 0, 0, A);
+    if (ncoop) hipLaunchKernelGGL(json_coop_index_kernel<false>, dim3(cgrid), dim3(256), 0, 0, A);
+    if (nycoop) hipLaunchKernelGGL(yaml_coop_index_kernel<false>, dim3(ygrid), dim3(256), 0, 0, A);
     JCHK(hipGetLastError());
     JCHK(hipEventRecord(e1));
     JCHK(hipEventSynchronize(e1));
@@ -1003,18 +1056,45 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     std::vector<uint32_t> ntok(n);
     JCHK(hipMemcpy(ntok.data(), d_ntok.p, n * 4, hipMemcpyDeviceToHost));
     std::vector<uint64_t> tbase(n, 0);
-    uint64_t ntoks = 0;
+    uint64_t ntoks = 0, nlines = 0;
     for (uint32_t k : coop_list) { tbase[k] = ntoks; ntoks += ntok[k]; }
+    for (uint32_t k : ycoop_list) { tbase[k] = nlines; nlines += ntok[k]; }
     JCHK(hipMemcpy(d_tokbase.p, tbase.data(), n * 8, hipMemcpyHostToDevice));
-    d_toks.alloc(ntoks); d_aux.alloc(ntoks);
-    A.toks = d_toks.p; A.aux = d_aux.p;
+    d_toks.alloc(ntoks); d_aux.alloc(ntoks); d_ylines.alloc(nlines);
+    A.toks = d_toks.p; A.aux = d_aux.p; A.ylines = d_ylines.p;
     JCHK(hipEventRecord(e0));
-    hipLaunchKernelGGL(json_coop_index_kernel<true>, dim3(cgrid), dim3(256), 0, 0, A);
-    hipLaunchKernelGGL(json_coop_tree_kernel, dim3(cgrid), dim3(256), 0, 0, A);
+    if (ncoop) {
+      hipLaunchKernelGGL(json_coop_index_kernel<true>, dim3(cgrid), dim3(256), 0, 0, A);
+      hipLaunchKernelGGL(json_coop_tree_kernel, dim3(cgrid), dim3(256), 0, 0, A);
+    }
+    if (nycoop) {
+      hipLaunchKernelGGL(yaml_coop_index_kernel<true>, dim3(ygrid), dim3(256), 0, 0, A);
+      hipLaunchKernelGGL(yaml_coop_segment_kernel<false>, dim3(ygrid), dim3(256), 0, 0, A);
+    }
     JCHK(hipGetLastError());
     JCHK(hipEventRecord(e1));
     JCHK(hipEventSynchronize(e1));
     JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
+    if (nycoop) {
+      std::vector<uint32_t> nseg(n);
+      JCHK(hipMemcpy(nseg.data(), d_nseg.p, n * 4, hipMemcpyDeviceToHost));
+      std::vector<uint64_t> sbase(n, 0);
+      uint64_t nsegs = 0;
+      for (uint32_t k : ycoop_list) { sbase[k] = nsegs; nsegs += nseg[k]; }
+      JCHK(hipMemcpy(d_segbase.p, sbase.data(), n * 8, hipMemcpyHostToDevice));
+      d_ysegs.alloc(nsegs);
+      JCHK(hipMemset(d_ysegs.p, 0xFF, std::max<uint64_t>(nsegs, 1) * sizeof(YSeg)));   // (a segment nobody writes names no document)
+      A.ysegs = d_ysegs.p; A.nsegs = nsegs;
+      sgrid = grid_for(std::max<uint64_t>(nsegs, 1), 256);
+      JCHK(hipEventRecord(e0));
+      hipLaunchKernelGGL(yaml_coop_segment_kernel<true>, dim3(ygrid), dim3(256), 0, 0, A);
+      hipLaunchKernelGGL(yaml_coop_parse_kernel<M_COUNT>, dim3(sgrid), dim3(256), 0, 0, A);
+      hipLaunchKernelGGL(yaml_coop_fix_kernel, dim3(ygrid), dim3(256), 0, 0, A);
+      JCHK(hipGetLastError());
+      JCHK(hipEventRecord(e1));
+      JCHK(hipEventSynchronize(e1));
+      JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
+    }
     mark("cooperative index + tree");
   }
   if (bad_now()) return false;
@@ -1100,6 +1180,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     hipLaunchKernelGGL(json_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (yaml_on) hipLaunchKernelGGL(yaml_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (ncoop) hipLaunchKernelGGL(json_coop_emit_kernel, dim3(cgrid), dim3(256), 0, 0, A);
+    if (nycoop) hipLaunchKernelGGL(yaml_coop_parse_kernel<M_EMIT>, dim3(sgrid), dim3(256), 0, 0, A);
 #if !GG_JDIAG_NOINTERN
     hipLaunchKernelGGL(json_own_kernel, dim3(grid_for(tslots, 256)), dim3(256), 0, 0, A);
     hipLaunchKernelGGL(json_fix_verify_kernel, dim3(grid_for(n * 64ull, 256)), dim3(256), 0, 0, A);
@@ -1160,6 +1241,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   st.refused_docs = refused ? refused->size() : 0;
   st.coop_docs = 0;
   for (uint32_t k : coop_list) st.coop_docs += doc_bad[k] == 0;
+  for (uint32_t k : ycoop_list) st.coop_docs += doc_bad[k] == 0;
   mark("doc_bad");
 
   // results to the host batch (the host keeps the reporter's columns and the intern index)

@@ -307,22 +307,50 @@ struct YF {
   uint32_t slot, k, first, j, cnt;
 };
 
-template <uint32_t MODE>
-__device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs& A, uint32_t d) {
+// A segment of a document for the cooperative path (yaml_coop.inc): one entry of a block collection with
+// everything under it, parsed by parse_yaml_doc<MODE, true> started from this descriptor instead of the
+// document's first byte.  The first segment (YS_FIRST) starts as a document does and leaves the root
+// collection open; every other one starts at a line start inside the open frame `f` (f.j: the entry's
+// ordinal).  A segment whose entry is a split `key:` header leaves that key's collection open too: the
+// collections a segment leaves open are its spine (`nspine`, the first it opens; kind, indentation and
+// child count as the segmentation kernel predicts them).
+enum : uint32_t { YS_FIRST = 1, YS_WHOLE = 2 };
+struct YSeg {
+  uint32_t doc, start, end, line;   // the text range (document offsets; start is a line start) and its first line
+  uint32_t flags, hdr, hu;          // the frame it starts in: spine container hu of this document's segment hdr
+  uint32_t nspine, skind[2], scnt[2];
+  int32_t sindent[2];
+  YF f;                             // the open frame (fix kernel; f.j by the segmentation kernel)
+  uint32_t nn, nc, ns;              // count pass: nodes, containers, strings
+  uint32_t cbase, next;             // fix kernel: the first container ordinal and children-block slot
+};
+
+template <uint32_t MODE, bool SEG = false>
+__device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs& A, uint32_t d, YSeg* seg = nullptr) {
   const uint64_t b0 = A.off[d], b1 = A.off[d + 1];
-  Text T(A.text, b0, b1 - b0);
+  Text T(A.text, b0, SEG ? (uint64_t)seg->end : b1 - b0);
   uint64_t i = 0, ls = 0;
   uint32_t line = 0, cont = 0;
   bool ok = true;
   auto column = [&]() __attribute__((always_inline)) { return (uint32_t)(i - ls) - cont; };
   auto bad = [&](uint32_t why) __attribute__((always_inline)) {
-    if (!A.doc_bad[d]) { A.doc_bad[d] = why; if (A.bad_at) A.bad_at[d] = (uint32_t)i; }
+    if (SEG) {
+      // a document's segments refuse it concurrently: the first reason stands, with its position (which
+      // segment is first may differ from run to run when several refuse)
+      if (atomicCAS(&A.doc_bad[d], 0u, why) == 0u && A.bad_at) A.bad_at[d] = (uint32_t)i;
+    } else if (!A.doc_bad[d]) { A.doc_bad[d] = why; if (A.bad_at) A.bad_at[d] = (uint32_t)i; }
     ok = false;
   };
   const uint64_t nb = (MODE >= M_EMIT) ? A.node_base[d] : 0;
   const uint32_t nlimit = (MODE >= M_EMIT) ? A.n_nodes[d] : 0xFFFFFFFFu;
-  const uint64_t cb = b0 >> 1, kcap = (b1 - b0) >> 1;
+  // a segment's count pass numbers its containers from 0 and leaves their child counts at its own half
+  // text offset in A.ycnt; the fix kernel moves them to the document's container order
+  const bool seg_count = SEG && MODE == M_COUNT;
+  uint16_t* const cnts = seg_count ? A.ycnt : A.counts;
+  const uint64_t cb = (b0 >> 1) + (seg_count ? seg->start >> 1 : 0u);
+  const uint64_t kcap = seg_count ? (seg->end - seg->start) >> 1 : (b1 - b0) >> 1;
   uint32_t nn = 1, nc = 0, ns = 0, ci = 0, next = 1;
+  if (SEG && MODE >= M_EMIT) { ci = seg->cbase; next = seg->next; }
   // the open collections: the innermost in registers (`top`), the ones around it in st[0, sp - 1) (scratch)
   YF st[kYMaxDepth];
   YF top{};
@@ -452,7 +480,7 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
     nc++;
     uint32_t cnt = 0, first = 0;
     if (MODE >= M_EMIT) {
-      cnt = A.counts[cb + k];
+      cnt = cnts[cb + k];
       first = next;
       next += cnt;
       if (next > nlimit || (kind == Y_FN && cnt != 1)) { bad(BAD_YAML); return false; }
@@ -471,7 +499,7 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
     YF& f = top;
     if (MODE == M_COUNT) {
       if (f.j > 0xFFFFu) { bad(BAD_WIDE); return false; }
-      A.counts[cb + f.k] = (uint16_t)f.j;
+      cnts[cb + f.k] = (uint16_t)f.j;
     } else if (f.j != f.cnt) { bad(BAD_YAML); return false; }
     sp--;
     if (sp) top = st[sp - 1];
@@ -695,18 +723,21 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
   };
 
   // ---- the document: leading blank and comment lines, an optional `---` line, the root at column 0
-  for (;;) {
-    sp_skip();
-    const uint32_t c = T.at(i);
-    if (c == '\n') { newline(); continue; }
-    if (c == '#') { if (!skip_comment()) return; continue; }
-    break;
+  const bool at_start = !SEG || (seg->flags & YS_FIRST);   // (a later segment starts at a line inside its frame)
+  if (at_start) {
+    for (;;) {
+      sp_skip();
+      const uint32_t c = T.at(i);
+      if (c == '\n') { newline(); continue; }
+      if (c == '#') { if (!skip_comment()) return; continue; }
+      break;
+    }
+    if (i == ls && T.at(i) == '-' && T.at(i + 1) == '-' && T.at(i + 2) == '-' && yblank(T.at(i + 3))) {
+      i += 3;
+      if (!end_line()) return;
+    }
+    if (!next_line()) { if (ok) bad(BAD_YAML); return; }
   }
-  if (i == ls && T.at(i) == '-' && T.at(i + 1) == '-' && T.at(i + 2) == '-' && yblank(T.at(i + 3))) {
-    i += 3;
-    if (!end_line()) return;
-  }
-  if (!next_line()) { if (ok) bad(BAD_YAML); return; }
   // state: S_NODE (a node for n_rel at i), S_LINE (at the first content byte of a line, column ccol, or
   // the end), S_AFTER (an inline value just ended mid-line)
   enum : uint32_t { S_NODE = 0, S_LINE = 1, S_AFTER = 2 };
@@ -714,8 +745,20 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
   int32_t n_pn = -1;
   bool eof = false;
   uint32_t ccol = 0;
-  if (column() != 0) { bad(BAD_YAML); return; }
+  if (at_start && column() != 0) { bad(BAD_YAML); return; }
   no_key();
+  // the frames a segment leaves open: the one it starts in and its spine
+  const uint32_t prot = SEG ? seg->nspine + (at_start ? 0u : 1u) : 0u;
+  if (!at_start) {
+    i = seg->start; ls = i; line = seg->line;
+    nn = 0;
+    top = seg->f;
+    sp = 1;
+    eof = !next_line();
+    if (!ok) return;
+    ccol = eof ? 0 : column();
+    state = S_LINE;
+  }
   while (ok) {
     if (state == S_AFTER) {
       close_fns();
@@ -727,6 +770,27 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
       continue;
     }
     if (state == S_LINE) {
+      if (SEG && sp <= prot) {
+        // at a frame this segment leaves open.  The end of the segment: exactly those frames are open, each
+        // one entry further, the spine as predicted.  Another line: it opens the frame's one entry here, at
+        // the frame's column -- a shallower line would close the frame, a second entry is the next
+        // segment's: the document was split where no entry starts, and is refused
+        if (eof) {
+          bool fine = sp == prot;
+          for (uint32_t t = 1; fine && t <= prot; t++) {
+            const YF& fr = t == sp ? top : st[t - 1];
+            if (t == 1 && !at_start) { fine = fr.j == seg->f.j + 1; continue; }
+            const uint32_t u = t - (at_start ? 1u : 2u);
+            fine = fr.kind == seg->skind[u] && fr.indent == seg->sindent[u] && fr.j == 1;
+          }
+          if (!fine) bad(BAD_YAML);
+          break;
+        }
+        if (sp && (top.j != (sp == 1 && !at_start ? seg->f.j : 0u) || ccol != (uint32_t)(top.indent & 0xFFFF))) {
+          bad(BAD_YAML);
+          return;
+        }
+      }
       if (!sp) { if (!eof) bad(BAD_YAML); break; }
       YF& F = top;
       const int32_t ind = F.indent & 0xFFFF;
@@ -913,6 +977,10 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
     state = S_AFTER;
   }
   if (!ok) return;
+  if (SEG) {
+    if (MODE == M_COUNT) { seg->nn = nn; seg->nc = nc; seg->ns = ns; }
+    return;
+  }
   if (sp) { bad(BAD_YAML); return; }
   if (MODE == M_COUNT) { A.n_nodes[d] = nn; A.n_cont[d] = nc; A.n_str[d] = ns; }
 }

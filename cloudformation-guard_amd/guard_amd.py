@@ -611,7 +611,10 @@ class Session:
         """Parses and interns strict-JSON documents on the MI355X (empty session only).  A document
         outside the device subset is built by the host loader at its position (stats["refused_docs"]
         counts them).  Returns the loader statistics, or None when the batch is refused as a whole
-        (a batch-wide limit: nothing loaded)."""
+        (a batch-wide limit: nothing loaded).  Documents of GG_JSON_COOP_MIN bytes or more (default 65536) are
+        parsed cooperatively: JSON by a workgroup each, block-style YAML -- unless
+        GG_YAML_COOP=0 -- cut into segments by a workgroup and parsed a lane per segment; stat(STAT["coop_docs"])
+        counts both."""
         n = len(texts)
         bufs = [_b(t) for t in texts]
         T = (ctypes.c_char_p * n)(*bufs)

@@ -314,7 +314,10 @@ int32_t gg_session_add_synthetic(gg_session *s, uint64_t first, size_t n, int32_
  * A document outside the device subset (libyaml-only syntax, duplicate keys, nesting past 64, a float
  * beyond the exact fast path, a raw character libyaml reads specially) is built by the host loader
  * and spliced in at its position.  A JSON document of GG_JSON_COOP_MIN bytes or more (default 65536; 0:
- * every JSON document) is parsed by a workgroup instead of a lane, with the same result;
+ * every JSON document) is parsed by a workgroup instead of a lane, with the same result; with
+ * GG_YAML_COOP unset or 1 (0: off) a block-style YAML document of that size is cut into segments by a
+ * workgroup and parsed a lane per segment, the same threshold for both formats (GG_YAML_DEVICE=0 turns
+ * every YAML path off);
  * gg_session_stat(s, 24) counts the documents the last load parsed that way.  Returns 0 when loaded, 1 when the batch is refused as a whole
  * (a batch-wide limit, or a refused document the host loader rejects too: nothing loaded, err->message
  * says why; gg_session_add_docs reports the loader error), -1 on error.  stats (may be NULL, 10 doubles):
