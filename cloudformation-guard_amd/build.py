@@ -25,7 +25,7 @@ YAML_LIB = "/opt/conda/lib"
 
 HOST_SRCS = ["doc_loader.cpp", "rules_parser.cpp", "regex_dfa.cpp", "cruet.cpp", "compiler.cpp", "reporter.cpp",
              "synth_corpus.cpp"]
-HIP_SRCS = ["eval_kernel.hip", "eval_kernel_nfa.hip", "json_gpu.hip", "merge_gpu.hip", "report_gpu.hip", "report_yaml_gpu.hip",
+HIP_SRCS = ["eval_kernel.hip", "eval_kernel_nfa.hip", "json_gpu.hip", "merge_gpu.hip", "append_gpu.hip", "report_gpu.hip", "report_yaml_gpu.hip",
             "report_junit_gpu.hip", "order_sort.hip", "capi.cpp"]
 # occupancy target of the lane-mode kernel (waves per SIMD); it caps VGPRs at 512 / N.  4 (126 VGPRs,
 # 8 spilled) beats 2 (178) and 3 (168): the kernel waits on dependent loads, so resident waves are
@@ -50,6 +50,7 @@ SRC_FLAGS["eval_kernel_nfa.hip"] = SRC_FLAGS["eval_kernel.hip"]
 SRC_FLAGS["report_yaml_gpu.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SRC_FLAGS["report_junit_gpu.hip"] = SRC_FLAGS["report_yaml_gpu.hip"]
 SRC_FLAGS["merge_gpu.hip"] = SRC_FLAGS["report_yaml_gpu.hip"]
+SRC_FLAGS["append_gpu.hip"] = SRC_FLAGS["report_yaml_gpu.hip"]
 
 
 def _obj(obj_dir, s):

@@ -32,6 +32,7 @@
 #include "eval_device.h"
 #include "host_format.h"
 #include "json_gpu.h"
+#include "append_gpu.h"
 #include "eisel_lemire.h"
 #include "yaml_scalar.h"
 #include "shortest_f64.h"
@@ -198,6 +199,18 @@ struct DBuf {
     if (count <= cap && p) { n = count; return; }
     alloc(count + count / 4 + 64);
     n = count;
+  }
+  // alloc that keeps the first `keep` elements (keep 0: alloc): a buffer that has to grow doubles, and the
+  // kept range moves device to device on `s`, which is drained before the old block is freed
+  void grow_keep(size_t count, size_t keep, hipStream_t s) {
+    if (!keep || !p || count <= cap) { alloc(count); return; }
+    DBuf<T> nb;
+    nb.alloc(std::max(count, 2 * cap));
+    HIPCHK(hipMemcpyAsync(nb.p, p, std::min(keep, count) * sizeof(T), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    dev_free_sync(p);
+    p = nb.p; cap = nb.cap; n = count;
+    nb.p = nullptr; nb.cap = 0; nb.n = 0;
   }
   void upload(const T* src, size_t count, hipStream_t s) {
     alloc(count);
@@ -423,6 +436,16 @@ struct gg_session {
   // empty on the host and live in HBM (dev_nodes, resident.*) until a host consumer needs them
   // (ensure_host_arena); dev_nodes then outlives the upload
   ResidentArena resident;
+  // nodes the resident blocks (dev_nodes, resident.*) have room for once a device append has grown them
+  // (0: exactly resident.nodes); they grow by doubling, so appends copy each resident node O(1) times
+  size_t arena_cap = 0;
+  // what the buffer set (dv) holds of this session's documents since the last upload: packed nodes, pool
+  // bytes, and the resource map / type column of packed_docs documents built with these two key ids.
+  // Documents are only appended (DocBatch), so the next upload packs and derives what follows and keeps
+  // the rest; all zero: nothing to keep (a fresh buffer set, a failed upload)
+  size_t packed_nodes = 0, packed_pool = 0, packed_docs = 0, packed_tix = 0;
+  uint32_t packed_rkey = NONE, packed_tkey = NONE;
+  std::vector<uint32_t> up_rmap, up_toff;   // host copies of d_res_map / d_tix_off for packed_docs documents
   std::mutex arena_mu;
   unsigned long long* ext_counts = nullptr;   // caller-owned device tally buffer (RCCL all-reduce)
   bool launched = false;
@@ -529,6 +552,7 @@ void ensure_host_arena(gg_session* s) {
   HIPCHK(hipMemcpy(D.kcol.data(), s->resident.kcol, N * 4, hipMemcpyDeviceToHost));
   for (uint32_t* p : {s->resident.line, s->resident.col, s->resident.kline, s->resident.kcol}) dev_free(p);
   s->resident = ResidentArena{};
+  s->arena_cap = 0;
   // the upload packed its arena already: the unpacked copy is no longer needed
   if (s->uploaded) { dev_free(s->dev_nodes); s->dev_nodes = nullptr; s->dev_nodes_n = 0; }
 }
@@ -541,34 +565,41 @@ void session_upload(gg_session* s) {
     if (trace) fprintf(stderr, "[upload] %-22s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tu).count());
   };
   if (s->dv && s->dv->device != s->device) { release_bufs(s->dv); s->dv = nullptr; HIPCHK(hipSetDevice(s->device)); }
-  if (!s->dv) s->dv = acquire_bufs(s->device);
+  if (!s->dv) { s->dv = acquire_bufs(s->device); s->packed_nodes = s->packed_pool = s->packed_docs = s->packed_tix = 0; }
   hipStream_t st = s->dv->stream;
+  // what the last upload left in the buffers; the session's record of it is void until this upload has replaced it
+  const size_t keep_nodes = s->packed_nodes <= arena_nodes(s) ? s->packed_nodes : 0;
+  const size_t keep_pool = keep_nodes && s->packed_pool <= s->docs.bytes.size() ? s->packed_pool : 0;
+  const size_t keep_docs = keep_nodes && s->packed_docs <= s->docs.ndocs() && s->up_rmap.size() == s->packed_docs &&
+                                   s->up_toff.size() == s->packed_docs ? s->packed_docs : 0;
+  const size_t keep_tix = s->packed_tix;
+  s->packed_nodes = s->packed_pool = s->packed_docs = s->packed_tix = 0;
   {
     // host arena (32 B nodes) -> device arena (16 B packed nodes + key-length column)
     const size_t n = arena_nodes(s);
     // lane-mode tiles address their document by a 32-bit global node index (eval_core.inc Ctx)
     if (n >= 0xFFFFFFFFull) throw std::runtime_error("batch too large for one session: split it (>= 2^32 arena nodes)");
+    // nodes [0, keep_nodes) are packed in the buffers already (an upload, then documents appended): only
+    // the range behind them is packed, from `src` = node keep_nodes
+    const size_t add = n - keep_nodes;
     DBuf<DNode> tmp;
     const DNode* src = nullptr;
-    if (s->dev_nodes && s->dev_nodes_n <= n) {
-      // the device loader's nodes are already in HBM: only nodes the host appended since (documents
-      // the device refused, built by the host loader) cross PCIe
-      if (s->dev_nodes_n == n) {
-        src = (const DNode*)s->dev_nodes;
-      } else {
-        tmp.alloc(n);
-        HIPCHK(hipMemcpyAsync(tmp.p, s->dev_nodes, s->dev_nodes_n * sizeof(DNode), hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(tmp.p + s->dev_nodes_n, s->docs.nodes.data() + s->dev_nodes_n,
-                              (n - s->dev_nodes_n) * sizeof(DNode), hipMemcpyHostToDevice, st));
-        src = tmp.p;
-      }
+    if (s->dev_nodes && s->dev_nodes_n == n) {
+      src = (const DNode*)s->dev_nodes + keep_nodes;
     } else {
-      tmp.upload(s->docs.nodes.data(), n, st);
+      // the device loader's nodes are already in HBM: only nodes the host appended since (documents
+      // the device refused, built by the host loader, host-loaded batches) cross PCIe
+      const size_t dn = s->dev_nodes && s->dev_nodes_n <= n ? s->dev_nodes_n : 0, h0 = std::max(dn, keep_nodes);
+      tmp.alloc(std::max<size_t>(add, 1));
+      if (dn > keep_nodes)
+        HIPCHK(hipMemcpyAsync(tmp.p, (const DNode*)s->dev_nodes + keep_nodes, (dn - keep_nodes) * sizeof(DNode), hipMemcpyDeviceToDevice, st));
+      if (n > h0)
+        HIPCHK(hipMemcpyAsync(tmp.p + (h0 - keep_nodes), s->docs.nodes.data() + h0, (n - h0) * sizeof(DNode), hipMemcpyHostToDevice, st));
       src = tmp.p;
     }
-    s->dv->d_nodes.alloc(std::max<size_t>(n, 1));
-    s->dv->d_klen.alloc(std::max<size_t>(n, 1));
-    s->dv->d_parent.alloc(std::max<size_t>(n, 1));
+    s->dv->d_nodes.grow_keep(std::max<size_t>(n, 1), keep_nodes, st);
+    s->dv->d_klen.grow_keep(std::max<size_t>(n, 1), keep_nodes, st);
+    s->dv->d_parent.grow_keep(std::max<size_t>(n, 1), keep_nodes, st);
     s->marks_on_device = false;
     s->rtab_ready = false;
     s->fetched_on_device = false;
@@ -576,10 +607,10 @@ void session_upload(gg_session* s) {
     DBuf<uint32_t> bad;
     bad.alloc(1);
     HIPCHK(hipMemsetAsync(bad.p, 0, 4, st));
-    if (n) {
-      const uint32_t blocks = (uint32_t)std::min<size_t>((n + 255) / 256, (size_t)dev_ncu(s->device) * 64);
-      hipLaunchKernelGGL(pack_nodes_kernel, dim3(blocks), dim3(256), 0, st, src, s->dv->d_nodes.p, s->dv->d_klen.p, s->dv->d_parent.p,
-                         (uint64_t)n, bad.p);
+    if (add) {
+      const uint32_t blocks = (uint32_t)std::min<size_t>((add + 255) / 256, (size_t)dev_ncu(s->device) * 64);
+      hipLaunchKernelGGL(pack_nodes_kernel, dim3(blocks), dim3(256), 0, st, src, s->dv->d_nodes.p + keep_nodes, s->dv->d_klen.p + keep_nodes,
+                         s->dv->d_parent.p + keep_nodes, (uint64_t)add, bad.p);
       HIPCHK(hipGetLastError());
     }
     uint32_t b = 0;
@@ -591,7 +622,12 @@ void session_upload(gg_session* s) {
     if (b & 4u) throw std::runtime_error("arena invariant broken: a string id is not a 16-byte pool slot");
     mark("packed");
   }
-  s->dv->d_bytes.upload(s->docs.bytes.data(), s->docs.bytes.size() ? s->docs.bytes.size() : 1, st);
+  {
+    // the pool only grows at its end: the bytes behind the uploaded ones follow them
+    const size_t pb = s->docs.bytes.size();
+    s->dv->d_bytes.grow_keep(pb ? pb : 1, keep_pool, st);
+    if (pb > keep_pool) HIPCHK(hipMemcpyAsync(s->dv->d_bytes.p + keep_pool, s->docs.bytes.data() + keep_pool, pb - keep_pool, hipMemcpyHostToDevice, st));
+  }
   s->dv->d_roots.upload(s->docs.roots.data(), s->docs.roots.size(), st);
   s->dv->d_base.upload(s->docs.base.data(), s->docs.base.size(), st);
   {
@@ -602,6 +638,14 @@ void session_upload(gg_session* s) {
     size_t nd = D.ndocs();
     std::vector<uint32_t> rmap(std::max<size_t>(nd, 1), NONE), toff(std::max<size_t>(nd, 1), 0);   // one entry at least: the uploads below
     size_t total = 0;
+    // documents [0, d0) have their map entry and type column in the buffers from the last upload (the same
+    // two key ids: string ids do not change once given): only the documents behind them are scanned
+    const size_t d0 = keep_docs <= nd && rkey == s->packed_rkey && s->type_key == s->packed_tkey ? keep_docs : 0;
+    if (d0) {
+      std::copy(s->up_rmap.begin(), s->up_rmap.end(), rmap.begin());
+      std::copy(s->up_toff.begin(), s->up_toff.end(), toff.begin());
+      total = keep_tix;
+    }
     // a resident arena: the first documents' nodes (the type-frequency sample below) come down, and the
     // root scan runs on the device (root_resources_kernel, json_gpu.hip)
     std::vector<DNode> sample;
@@ -613,21 +657,24 @@ void session_upload(gg_session* s) {
       HIPCHK(hipMemcpyAsync(sample.data(), s->dev_nodes, sn * sizeof(DNode), hipMemcpyDeviceToHost, st));
       HN = sample.data();
       if (rkey != NONE && s->type_key != NONE) {
-        DBuf<uint32_t> d_rm, d_cnt;
-        d_rm.alloc(nd); d_cnt.alloc(nd);
-        hipLaunchKernelGGL(root_resources_kernel, dim3(std::min<uint32_t>((uint32_t)((nd + 255) / 256), dev_ncu(s->device) * 16)),
-                           dim3(256), 0, st, (const DNode*)s->dev_nodes, s->dv->d_base.p, s->dv->d_roots.p, (uint32_t)nd, rkey,
-                           d_rm.p, d_cnt.p);
-        HIPCHK(hipGetLastError());
-        std::vector<uint32_t> cnt(nd);
-        HIPCHK(hipMemcpyAsync(rmap.data(), d_rm.p, nd * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, nd * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (size_t d = 0; d < nd; d++) { toff[d] = (uint32_t)total; total += cnt[d]; }
+        const size_t na = nd - d0;
+        if (na) {
+          DBuf<uint32_t> d_rm, d_cnt;
+          d_rm.alloc(na); d_cnt.alloc(na);
+          hipLaunchKernelGGL(root_resources_kernel, dim3(std::min<uint32_t>((uint32_t)((na + 255) / 256), dev_ncu(s->device) * 16)),
+                             dim3(256), 0, st, (const DNode*)s->dev_nodes, s->dv->d_base.p + d0, s->dv->d_roots.p + d0, (uint32_t)na, rkey,
+                             d_rm.p, d_cnt.p);
+          HIPCHK(hipGetLastError());
+          std::vector<uint32_t> cnt(na);
+          HIPCHK(hipMemcpyAsync(rmap.data() + d0, d_rm.p, na * 4, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, na * 4, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipStreamSynchronize(st));
+          for (size_t d = d0; d < nd; d++) { toff[d] = (uint32_t)total; total += cnt[d - d0]; }
+        }
       }
       HIPCHK(hipStreamSynchronize(st));
     } else if (rkey != NONE && s->type_key != NONE) {
-      for (size_t d = 0; d < nd; d++) {
+      for (size_t d = d0; d < nd; d++) {
         const DNode* N = D.nodes.data() + D.base[d];
         const DNode& root = N[D.roots[d]];
         toff[d] = (uint32_t)total;
@@ -641,12 +688,13 @@ void session_upload(gg_session* s) {
       }
     }
     mark("resource map");
-    if (total > 0xFFFFFFF0u) { std::fill(rmap.begin(), rmap.end(), NONE); total = 0; }
+    const bool no_column = total > 0xFFFFFFF0u;
+    if (no_column) { std::fill(rmap.begin(), rmap.end(), NONE); total = 0; }
     s->has_order = false;
 
     s->dv->d_res_map.upload(rmap.data(), std::max<size_t>(nd, 1), st);
     s->dv->d_tix_off.upload(toff.data(), std::max<size_t>(nd, 1), st);
-    s->dv->d_tix.alloc(std::max<size_t>(total, 1));
+    s->dv->d_tix.grow_keep(std::max<size_t>(total, 1), d0 && !no_column ? keep_tix : 0, st);
     // the column is a property of the documents (the Type string id of each Resources entry), so it
     // is built once per upload with the packed arena, not per evaluation
     if (s->type_key != NONE && nd) {
@@ -654,9 +702,14 @@ void session_upload(gg_session* s) {
       B.nodes = s->dv->d_nodes.p; B.klen = s->dv->d_klen.p; B.bytes = s->dv->d_bytes.p; B.roots = s->dv->d_roots.p;
       B.base = s->dv->d_base.p; B.ndocs = (uint32_t)nd;
       B.res_map = s->dv->d_res_map.p; B.tix_off = s->dv->d_tix_off.p; B.tix = s->dv->d_tix.p; B.type_key = s->type_key;
-      const uint32_t blocks = std::min<uint32_t>((B.ndocs + 3) / 4, dev_ncu(s->device) * 16);
-      hipLaunchKernelGGL(resource_type_kernel, dim3(blocks), dim3(256), 0, st, B);
-      HIPCHK(hipGetLastError());
+      // the column of the documents behind d0 (the per-document arrays shifted; bases and column offsets are global)
+      DevBatch Bn = B;
+      Bn.base = B.base + d0; Bn.res_map = B.res_map + d0; Bn.tix_off = B.tix_off + d0; Bn.ndocs = (uint32_t)(nd - d0);
+      if (Bn.ndocs) {
+        const uint32_t blocks = std::min<uint32_t>((Bn.ndocs + 3) / 4, dev_ncu(s->device) * 16);
+        hipLaunchKernelGGL(resource_type_kernel, dim3(blocks), dim3(256), 0, st, Bn);
+        HIPCHK(hipGetLastError());
+      }
       if (trace) { HIPCHK(hipStreamSynchronize(st)); mark("type column kernel"); }
       // Shape-sorted batches: the lane kernel's 64 lanes run in lock-step, so a batch costs the union
       // of its documents' paths.  Documents are ordered by their counts of the 8 most frequent Type
@@ -719,6 +772,11 @@ void session_upload(gg_session* s) {
     }
     HIPCHK(hipStreamSynchronize(st));   // the host vectors above die at the end of this scope
     mark("type column + order");
+    // the buffers now hold this much of the session (the pack above was waited for and checked)
+    s->packed_nodes = arena_nodes(s);
+    s->packed_pool = D.bytes.size();
+    s->packed_rkey = rkey; s->packed_tkey = s->type_key;
+    if (!no_column) { s->packed_docs = nd; s->packed_tix = total; s->up_rmap.assign(rmap.begin(), rmap.begin() + nd); s->up_toff.assign(toff.begin(), toff.begin() + nd); }
   }
   std::vector<DevProg> dps;
   s->max_top = 1;
@@ -4208,6 +4266,96 @@ int32_t gg_session_add_docs_device(gg_session* s, const char* const* texts, cons
   return add_docs_device(s, s->params.get(), texts, lens, names, n, stats, err);
 }
 
+// ---- appending a device-loaded batch (gpu_load_json with append_to = the session's batch) -------------
+// `b` is the complete new batch: its pool opens with the session's pool and its index covers both, its
+// nodes, bases, roots and names are its own documents'.  Both paths allocate everything first and change
+// the session only after the last step that can fail.
+static const auto make_room = [](auto& v, size_t extra) {   // amortised: appends copy a column O(1) times per element
+  if (v.capacity() < v.size() + extra) v.reserve(std::max(v.size() + extra, 2 * v.capacity()));
+};
+
+static void append_doc_index(DocBatch& D, DocBatch& b, uint64_t first_node) {   // room made: nothing here throws
+  D.bytes = std::move(b.bytes);
+  D.islots = std::move(b.islots); D.ilen = std::move(b.ilen); D.iused = b.iused;
+  for (size_t k = 0; k < b.ndocs(); k++) {
+    D.base.push_back(first_node + b.base[k]);
+    D.roots.push_back(b.roots[k]);
+    D.names.push_back(std::move(b.names[k]));
+  }
+}
+
+// the arena is on the host (GG_RESIDENT_ARENA=0, a host writer ran, host-built documents are present, or
+// the new batch has some): the batch's columns, brought down by the loader, go behind the host columns
+static void append_host(gg_session* s, DocBatch& b) {
+  DocBatch& D = s->docs;
+  const size_t oldN = arena_nodes(s), addN = b.nodes.size();
+  if (oldN + addN >= 0xFFFFFFFFull) throw std::runtime_error("batch too large for one session: split it (>= 2^32 arena nodes)");
+  // room first, for a resident arena's columns too (empty on the host until ensure_host_arena fills them
+  // into this room): an allocation that fails leaves the arena where it was
+  auto room = [&](auto& v) { if (v.capacity() < oldN + addN) v.reserve(std::max(oldN + addN, 2 * v.capacity())); };
+  room(D.nodes); room(D.line); room(D.col); room(D.kline); room(D.kcol);
+  make_room(D.base, b.ndocs()); make_room(D.roots, b.ndocs()); make_room(D.names, b.ndocs());
+  ensure_host_arena(s);
+  D.nodes.resize(oldN + addN); D.line.resize(oldN + addN); D.col.resize(oldN + addN); D.kline.resize(oldN + addN); D.kcol.resize(oldN + addN);
+  if (addN) {
+    memcpy(D.nodes.data() + oldN, b.nodes.data(), addN * sizeof(DNode));
+    memcpy(D.line.data() + oldN, b.line.data(), addN * 4);
+    memcpy(D.col.data() + oldN, b.col.data(), addN * 4);
+    memcpy(D.kline.data() + oldN, b.kline.data(), addN * 4);
+    memcpy(D.kcol.data() + oldN, b.kcol.data(), addN * 4);
+  }
+  append_doc_index(D, b, oldN);
+}
+
+// the arena is resident and so is the new batch: its columns are copied behind the resident ones device
+// to device.  The resident blocks grow by doubling: new blocks from the block cache, the resident nodes
+// copied device to device, and the old blocks handed back once the device has drained.
+static void append_resident(gg_session* s, DocBatch& b, DNode* add_nodes, const ResidentArena& add) {
+  bind_device(s);
+  DocBatch& D = s->docs;
+  const uint64_t oldN = s->resident.nodes, addN = add.nodes, need = oldN + addN;
+  if (need >= 0xFFFFFFFFull) throw std::runtime_error("batch too large for one session: split it (>= 2^32 arena nodes)");
+  make_room(D.base, b.ndocs()); make_room(D.roots, b.ndocs()); make_room(D.names, b.ndocs());
+  struct Cols { DNode* nodes = nullptr; uint32_t* m[4] = {nullptr, nullptr, nullptr, nullptr}; };
+  Cols cur, src;
+  cur.nodes = (DNode*)s->dev_nodes; src.nodes = add_nodes;
+  uint32_t* const curm[4] = {s->resident.line, s->resident.col, s->resident.kline, s->resident.kcol};
+  uint32_t* const addm[4] = {add.line, add.col, add.kline, add.kcol};
+  for (int c = 0; c < 4; c++) { cur.m[c] = curm[c]; src.m[c] = addm[c]; }
+  size_t cap = s->arena_cap ? s->arena_cap : (size_t)oldN;
+  struct Grown : Cols {   // blocks not yet the session's go back behind a fence on the stream that fills them
+    ~Grown() { dev_free_on(nodes, nullptr); for (uint32_t* p : m) dev_free_on(p, nullptr); }
+  } g;
+  const bool grow = need > cap;
+  if (grow) {
+    cap = (size_t)std::max<uint64_t>(need, 2 * (uint64_t)cap);
+    HIPCHK(dev_alloc(&g.nodes, cap * sizeof(DNode)));
+    HIPCHK(hipMemcpyAsync(g.nodes, cur.nodes, oldN * sizeof(DNode), hipMemcpyDeviceToDevice, nullptr));
+    for (int c = 0; c < 4; c++) {
+      HIPCHK(dev_alloc(&g.m[c], cap * 4));
+      HIPCHK(hipMemcpyAsync(g.m[c], cur.m[c], oldN * 4, hipMemcpyDeviceToDevice, nullptr));
+    }
+  }
+  // (without growth the range past oldN of the session's own blocks is written: nothing reads it before the commit)
+  const Cols& dst = grow ? (const Cols&)g : cur;
+  HIPCHK(hipMemcpyAsync(dst.nodes + oldN, src.nodes, addN * sizeof(DNode), hipMemcpyDeviceToDevice, nullptr));
+  for (int c = 0; c < 4; c++) HIPCHK(hipMemcpyAsync(dst.m[c] + oldN, src.m[c], addN * 4, hipMemcpyDeviceToDevice, nullptr));
+  // every stream, not only this one: the old blocks go back to the cache below
+  HIPCHK(hipDeviceSynchronize());
+  if (grow) {
+    dev_free(cur.nodes);
+    for (uint32_t* p : cur.m) dev_free(p);
+    s->dev_nodes = g.nodes;
+    s->resident.line = g.m[0]; s->resident.col = g.m[1]; s->resident.kline = g.m[2]; s->resident.kcol = g.m[3];
+    g.nodes = nullptr;
+    for (auto& p : g.m) p = nullptr;
+  }
+  s->arena_cap = cap;
+  s->resident.nodes = need;
+  s->dev_nodes_n = (size_t)need;
+  append_doc_index(D, b, oldN);
+}
+
 // gg_session_add_docs_device with the input parameters given (a shard's or a chunk's session shares one
 // read-only parameter batch): they are merged into every document on the device (merge_gpu.h), into the
 // documents the device refuses on the host; a failing merge is the first failing document's, code -1
@@ -4217,7 +4365,12 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
   try {
     std::string why;
     if (!ensure_device(why, s->device, &s->device)) { set_err(err, -1, why); return -1; }
-    if (s->docs.ndocs()) { set_err(err, 18, "IllegalArguments: the device loader fills an empty session"); return -1; }
+    // a session that holds documents is appended to: the batch loads with the session's strings seeded into
+    // the loader's intern table (append_gpu.h), then joins the arena where that lives -- behind the resident
+    // columns in HBM (append_resident), or behind the host columns when the arena is there.  Nothing below
+    // touches the session before the batch is complete and merged.
+    const bool appending = s->docs.ndocs() != 0;
+    if (appending && s->docs.serde) { set_err(err, 18, "IllegalArguments: the device loader builds libyaml-mode documents and the session holds serde-mode ones"); return -1; }
     // the lane passes give a document to one lane: a batch of few, large documents (Terraform plans of
     // thousands of resources) leaves the device nearly idle there -- 2048 plans parsed at 0.3 GB/s of text
     // (profiles/r04a_bench_cfg4_lane_2048.json) against ~1 GB/s on 16 host threads.  Large documents go to
@@ -4251,7 +4404,10 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
     const auto tl = std::chrono::steady_clock::now();
     ParamMerge pm;
     pm.params = params;
-    if (!gpu_load_json(b, texts, lens, nm, n, st, why, &refused, &dev_nodes, keep ? &res : nullptr, &pm)) { set_note(err, why); return 1; }
+    // an appended batch stays resident only beside a resident arena
+    const bool want_res = keep && (!appending || s->resident.nodes);
+    if (!gpu_load_json(b, texts, lens, nm, n, st, why, &refused, &dev_nodes, want_res ? &res : nullptr, &pm,
+                       appending ? &s->docs : nullptr)) { set_note(err, why); return 1; }
     struct ResHolder { ResidentArena& r; ~ResHolder() { for (uint32_t* p : {r.line, r.col, r.kline, r.kcol}) dev_free(p); } } rhold{res};
     if (getenv("GG_LOAD_TRACE"))
       fprintf(stderr, "[load] gpu_load_json returned %8.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl).count());
@@ -4295,14 +4451,24 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
       set_err(err, ffi_code(le.kind), error_display(le.kind, le.msg));
       return -1;
     }
-    s->docs = std::move(b);
-    s->uploaded = false;
-    dev_free(s->dev_nodes);
-    s->dev_nodes = dev_nodes; s->dev_nodes_n = res.nodes ? (size_t)res.nodes : dev_n;
-    dev_nodes = nullptr;
-    s->resident = res;
-    res = ResidentArena{};
-    s->coop_docs = st.coop_docs;
+    if (appending) {
+      if (res.nodes && s->resident.nodes) append_resident(s, b, (DNode*)dev_nodes, res);
+      else append_host(s, b);   // the batch's own device copies go back to the cache (hold, rhold)
+      s->uploaded = false;
+      s->evaluated = false;   // the tiles are the earlier documents' only
+      s->coop_docs += st.coop_docs;
+    } else {
+      s->docs = std::move(b);
+      s->packed_nodes = s->packed_pool = s->packed_docs = s->packed_tix = 0;
+      s->uploaded = false;
+      dev_free(s->dev_nodes);
+      s->dev_nodes = dev_nodes; s->dev_nodes_n = res.nodes ? (size_t)res.nodes : dev_n;
+      dev_nodes = nullptr;
+      s->resident = res;
+      s->arena_cap = 0;
+      res = ResidentArena{};
+      s->coop_docs = st.coop_docs;
+    }
     load_stats(st, stats);
     if (getenv("GG_LOAD_TRACE"))
       fprintf(stderr, "[load] session holds the batch %8.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl).count());

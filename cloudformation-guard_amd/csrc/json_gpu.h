@@ -62,6 +62,13 @@ struct ResidentArena {
 // document keeps its placeholder, unmerged: the caller merges the one it builds.  When a document's
 // merge fails the load still returns true with the first such document (in document order) in
 // merge->fail_doc and the reference's error in merge->fail; the batch is then not to be evaluated.
+//
+// With `append_to` (a batch that holds documents already; `out` is still a fresh batch) the load is one that
+// appends: every string of append_to's pool is seeded into the intern table under its id before the
+// new documents intern (append_gpu.h), so out.bytes opens with append_to's pool byte for byte, a string the
+// two share keeps its id, new strings follow, and out's index covers both.  st.distinct_strings and
+// st.pool_bytes count what the load added.  out's nodes, bases and roots are its own documents' only: the
+// caller puts them behind append_to's.
 struct ParamMerge {
   const DocBatch* params = nullptr;
   uint32_t fail_doc = NONE;
@@ -69,6 +76,7 @@ struct ParamMerge {
 };
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused = nullptr,
-                   void** keep_nodes = nullptr, ResidentArena* resident = nullptr, ParamMerge* merge = nullptr);
+                   void** keep_nodes = nullptr, ResidentArena* resident = nullptr, ParamMerge* merge = nullptr,
+                   const DocBatch* append_to = nullptr);
 
 }  // namespace gg

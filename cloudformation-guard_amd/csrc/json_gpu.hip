@@ -36,6 +36,7 @@
 #include "dev_cache.h"
 #include "host_pinned.h"
 #include "merge_gpu.h"
+#include "append_gpu.h"
 
 #include <algorithm>
 #include <chrono>
@@ -227,13 +228,6 @@ struct WordStream {
   __device__ void run(const struct Text& T, uint32_t k, uint32_t r, F&& on_word);
 };
 
-__device__ inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-
 // Decodes the JSON string whose opening quote is at `q`; calls sink(byte) per decoded byte.
 // Returns the index after the closing quote, or 0 when the string is outside the subset (bad
 // escapes, surrogate \u escapes, control bytes, malformed UTF-8, and the raw characters libyaml's
@@ -388,7 +382,7 @@ __device__ bool scalar(Text& T, uint64_t i, uint64_t L, DNode& d) {
 
 // insert-or-find a string fingerprint; returns its slot, or ~0u when the table is full
 __device__ uint32_t intern_slot(const JArgs& A, uint64_t key, uint32_t len, uint32_t doc, uint32_t q) {
-  uint64_t idx = mix64(key) & A.tmask;
+  uint64_t idx = intern_mix64(key) & A.tmask;   // append_gpu.h: the seeding kernel probes from the same slot
   for (uint32_t probe = 0; probe < 1024; probe++) {
     const unsigned long long k = A.tkey[idx];
     if (k == key) return (uint32_t)idx;
@@ -427,7 +421,7 @@ __device__ __attribute__((always_inline)) uint64_t string_occurrence(const JArgs
   fp.h = (hs.h ^ hs.ws.word) * 0x100000001b3ull;
   fp.len = hs.ws.len;
   if (EMIT) {
-    const uint64_t key64 = (mix64(fp.h ^ ((uint64_t)fp.len * 0x9E3779B97F4A7C15ull)) & A.fp_mask) | 1ull;
+    const uint64_t key64 = intern_key64(fp.h, fp.len, A.fp_mask);   // append_gpu.h: the seeding kernel derives the same key
 #if GG_JDIAG_NOINTERN
     const uint32_t s = (uint32_t)key64 & 1023u;
 #else
@@ -641,6 +635,7 @@ json_pass_kernel(JArgs A) {
 __global__ void __launch_bounds__(256) json_own_kernel(JArgs A) {
   for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s <= A.tmask; s += (uint64_t)gridDim.x * blockDim.x) {
     if (A.tkey[s] == 0) continue;
+    if (A.towner[s] == kSeededOwner) continue;   // an appended-to session's string: in the pool under its id already
     const uint32_t len = A.tlen[s];
     const uint64_t need = len ? (len + 15ull) & ~15ull : 16ull;   // as DocBatch::intern
     const unsigned long long at = atomicAdd(A.pool_cursor, (unsigned long long)need);
@@ -904,7 +899,7 @@ bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min, bool yam
 
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused,
-                   void** keep_nodes, ResidentArena* resident, ParamMerge* merge) {
+                   void** keep_nodes, ResidentArena* resident, ParamMerge* merge, const DocBatch* append_to) {
   if (merge && !merge->params) merge = nullptr;
   if (merge) merge->fail_doc = NONE;
   if (resident) *resident = ResidentArena{};
@@ -925,6 +920,26 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   }
   const uint64_t total = off[n];
   st.text_bytes = total;
+  // appending: the strings the session holds, ascending by pool offset (the seeding kernel's lanes read
+  // neighbouring pool slots), and its pool as the new pool's first bytes
+  std::vector<uint32_t> seed_off, seed_len;
+  const uint64_t seed_bytes = append_to ? append_to->bytes.size() : 0;
+  if (append_to) {
+    std::vector<uint64_t> sl;
+    sl.reserve(append_to->iused);
+    for (size_t k = 0; k < append_to->islots.size(); k++)
+      if (append_to->islots[k]) sl.push_back((uint64_t)(append_to->islots[k] - 1) << 32 | append_to->ilen[k]);
+    std::sort(sl.begin(), sl.end());
+    seed_off.resize(sl.size()); seed_len.resize(sl.size());
+    for (size_t k = 0; k < sl.size(); k++) {
+      seed_off[k] = (uint32_t)(sl[k] >> 32); seed_len[k] = (uint32_t)sl[k];
+      if ((seed_off[k] & 15u) || (uint64_t)seed_off[k] + ((seed_len[k] + 15ull) & ~15ull) > seed_bytes) {
+        why = "the session's string pool is not in 16-byte slots"; return false;
+      }
+    }
+    if (seed_bytes + 16 > 0xF0000000ull) { why = kWhy[BAD_POOL]; return false; }
+  }
+  const uint64_t nseed = seed_off.size();
   // one Staging per device, kept between loads (hipHostFree waits for the device to go idle, as hipFree
   // does); a concurrent load on the same device builds its own
   static std::mutex stg_mu[64];
@@ -1150,15 +1165,23 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   uint32_t start_log = 23;
   if (const char* e = getenv("GG_JSON_TABLE_LOG")) start_log = (uint32_t)std::max(16, std::min(28, atoi(e)));   // tests
   uint64_t tslots = 1ull << 16;
-  while (tslots < 2 * S && tslots < (1ull << start_log)) tslots <<= 1;
+  const uint64_t S_all = S + nseed;   // the seeded strings take a slot each
+  while (tslots < 2 * S_all && tslots < (1ull << start_log)) tslots <<= 1;
   DevArr<unsigned long long> d_tkey, d_towner, d_pool_cursor;
   DevArr<uint32_t> d_tlen, d_tid;
   d_pool_cursor.alloc(1);
   // pool: a quarter of the text to start with (templates repeat their strings); doubles when full,
   // up to the bound every distinct string fits in (its bytes + 16 of alignment padding)
-  const uint64_t pool_max = std::min<uint64_t>(total + 16 * S + 16, 0xF0000000ull);
-  uint64_t pool_cap = std::min<uint64_t>(std::max<uint64_t>(total / 4, 1ull << 20), pool_max);
-  DevArr<uint8_t> d_pool;
+  const uint64_t pool_max = std::min<uint64_t>(seed_bytes + total + 16 * S + 16, 0xF0000000ull);
+  uint64_t pool_cap = std::min<uint64_t>(seed_bytes + std::max<uint64_t>(total / 4, 1ull << 20), pool_max);
+  DevArr<uint8_t> d_pool, d_seed_pool;
+  DevArr<uint32_t> d_seed_off, d_seed_len;
+  if (nseed) {
+    d_seed_pool.alloc(seed_bytes); d_seed_off.alloc(nseed); d_seed_len.alloc(nseed);
+    JCHK(hipMemcpy(d_seed_pool.p, append_to->bytes.data(), seed_bytes, hipMemcpyHostToDevice));
+    JCHK(hipMemcpy(d_seed_off.p, seed_off.data(), nseed * 4, hipMemcpyHostToDevice));
+    JCHK(hipMemcpy(d_seed_len.p, seed_len.data(), nseed * 4, hipMemcpyHostToDevice));
+  }
   A.node_base = d_nbase.p; A.nodes = d_nodes.p;
   DevArr<NodeRec> d_recs;
   d_recs.alloc(N);
@@ -1170,13 +1193,17 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     A.pool = d_pool.p; A.pool_cursor = d_pool_cursor.p; A.pool_cap = pool_cap;
     d_tkey.alloc(tslots); d_towner.alloc(tslots); d_tlen.alloc(tslots); d_tid.alloc(tslots);
     JCHK(hipMemset(d_tkey.p, 0, tslots * 8));
-    JCHK(hipMemset(d_pool_cursor.p, 0, 8));
+    JCHK(hipMemcpy(d_pool_cursor.p, &seed_bytes, 8, hipMemcpyHostToDevice));
     JCHK(hipMemset(d_pool.p, 0, pool_cap + 16));
+    if (nseed) JCHK(hipMemcpy(d_pool.p, d_seed_pool.p, seed_bytes, hipMemcpyDeviceToDevice));
     JCHK(hipMemcpy(d_doc_bad.p, d_doc_bad0.p, n * 4, hipMemcpyDeviceToDevice));
     A.tkey = d_tkey.p; A.tlen = d_tlen.p; A.towner = d_towner.p; A.tid = d_tid.p; A.tmask = tslots - 1;
 
-    // 2. emit, 3. own, 4. fix + verify
+    // 2. emit, 3. own, 4. fix + verify; appending, the session's strings enter the table first
     JCHK(hipEventRecord(e0));
+    if (nseed)
+      append_seed_table(SeedTable{A.tkey, A.tlen, A.towner, A.tid, A.tmask, A.fp_mask, A.bad, BAD_TABLE}, d_pool.p, d_seed_off.p,
+                        d_seed_len.p, (uint32_t)nseed);
     hipLaunchKernelGGL(json_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (yaml_on) hipLaunchKernelGGL(yaml_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (ncoop) hipLaunchKernelGGL(json_coop_emit_kernel, dim3(cgrid), dim3(256), 0, 0, A);
@@ -1193,7 +1220,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     JCHK(hipEventElapsedTime(&ms, e0, e1)); ms_total += ms;
     uint32_t b = 0;
     JCHK(hipMemcpy(&b, d_bad.p, 4, hipMemcpyDeviceToHost));
-    if (b == BAD_TABLE && tslots < 2 * S && tslots < (1ull << 28)) {
+    if (b == BAD_TABLE && tslots < 2 * S_all && tslots < (1ull << 28)) {
       tslots <<= 1;
       JCHK(hipMemset(d_bad.p, 0, 4));
       st.table_retries++;
@@ -1267,8 +1294,10 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   };
   uint64_t distinct = 0;
   auto fetch_pool_index = [&]() {
+    // appending: the pool's first bytes are the session's own, and so is the start of the index
+    if (append_to) { out.bytes = append_to->bytes; out.islots = append_to->islots; out.ilen = append_to->ilen; out.iused = append_to->iused; }
     out.bytes.resize(pool_used);
-    if (pool_used) stg.d2h(&out.bytes[0], d_pool.p, pool_used);
+    if (pool_used > seed_bytes) stg.d2h(&out.bytes[seed_bytes], d_pool.p + seed_bytes, pool_used - seed_bytes);
     mark("arena D2H");
     std::vector<unsigned long long> tkey(tslots);
     std::vector<uint32_t> tlen(tslots), tid(tslots);
@@ -1279,7 +1308,8 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     mark("table D2H");
     std::vector<uint32_t> aoff, alen;
     aoff.reserve(tslots / 2); alen.reserve(tslots / 2);
-    for (uint64_t s = 0; s < tslots; s++) if (tkey[s]) { aoff.push_back(tid[s]); alen.push_back(tlen[s]); }
+    // (a seeded slot's id lies in the session's pool: indexed already)
+    for (uint64_t s = 0; s < tslots; s++) if (tkey[s] && tid[s] >= seed_bytes) { aoff.push_back(tid[s]); alen.push_back(tlen[s]); }
     distinct = aoff.size();
     mark("table scan");
     out.adopt_bulk(aoff.data(), alen.data(), aoff.size(), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
@@ -1322,7 +1352,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     for (size_t k = 0; k < n; k++) if (!doc_bad[k]) out.roots[k] = nn[k] + tmpl.np;
   out.base.assign(nbase.begin(), nbase.begin() + n);
   out.names.assign(names.begin(), names.begin() + n);
-  st.nodes = N; st.distinct_strings = distinct; st.pool_bytes = pool_used;
+  st.nodes = N; st.distinct_strings = distinct; st.pool_bytes = pool_used - seed_bytes;   // appending: what this load added
   mark("adopt + names");
   if (keep_nodes) { *keep_nodes = d_nodes.p; d_nodes.p = nullptr; }
   return true;

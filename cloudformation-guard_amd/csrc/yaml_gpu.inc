@@ -438,7 +438,7 @@ __device__ __attribute__((always_inline)) inline void parse_yaml_doc(const JArgs
     const uint64_t h = (hs.h ^ hs.ws.word) * 0x100000001b3ull;
     const uint32_t len = hs.ws.len;
     *len_out = len;
-    const uint64_t key64 = (mix64(h ^ ((uint64_t)len * 0x9E3779B97F4A7C15ull)) & A.fp_mask) | 1ull;
+    const uint64_t key64 = intern_key64(h, len, A.fp_mask);
     const uint32_t s = intern_slot(A, key64, len, d, q);
     if (s == ~0u) { refuse(A, BAD_TABLE); bad(BAD_TABLE); }
     return s;

@@ -608,8 +608,11 @@ class Session:
             _raise(err)
 
     def add_docs_device(self, texts, names=None):
-        """Parses and interns strict-JSON documents on the MI355X (empty session only).  A document
-        outside the device subset is built by the host loader at its position (stats["refused_docs"]
+        """Parses and interns JSON / block-style YAML documents on the MI355X.  A session that holds
+        documents already is appended to: strings the batches share keep their ids, the statistics count
+        what this call added, and the last evaluation is invalidated (eval() again before report()); a call
+        that fails or returns None leaves the session as it was.
+        A document outside the device subset is built by the host loader at its position (stats["refused_docs"]
         counts them).  Returns the loader statistics, or None when the batch is refused as a whole
         (a batch-wide limit: nothing loaded).  Documents of GG_JSON_COOP_MIN bytes or more (default 65536) are
         parsed cooperatively: JSON by a workgroup each, block-style YAML -- unless

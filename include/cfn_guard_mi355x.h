@@ -213,10 +213,10 @@ int32_t gg_session_tile_status(gg_session *s, uint8_t *out, size_t n);
 double gg_session_last_kernel_ms(gg_session *s);
 int32_t gg_device_available(void);
 /* Frees the device blocks the library keeps for reuse on `device` (-1: every device).  Freed loader
- * temporaries and session buffers are cached per device (bounded by GG_DEV_CACHE_GB, default 16)
+ * temporaries and session buffers are cached per device (bounded by GG_DEV_CACHE_GB, default 48)
  * because hipFree waits for the whole device to go idle; this hands them back, as
  * torch.cuda.empty_cache() does for torch's allocator.  The streamed entries' page-locked host staging
- * blocks (bounded by GG_PINNED_CACHE_GB per device, default 1) are unpinned and freed too.  Returns the
+ * blocks (bounded by GG_PINNED_CACHE_GB per device, default 2) are unpinned and freed too.  Returns the
  * bytes released (device and host). */
 int64_t gg_device_cache_release(int32_t device);
 
@@ -310,7 +310,15 @@ int32_t gg_session_add_synthetic(gg_session *s, uint64_t first, size_t n, int32_
 /* Device loader (replaces, for strict-JSON input, the reference's
  * Loader::load + PathAwareValue::try_from, guard/src/rules/libyaml/loader.rs:31-195 and
  * guard/src/rules/path_value.rs:414-478, as called from validate.rs:760-787).  Parses and interns
- * the documents on the MI355X into an EMPTY session, building the arena gg_session_add_docs builds.
+ * the documents on the MI355X, building the arena gg_session_add_docs builds.  A session that holds
+ * documents already (loaded by either loader) is appended to: the session's strings are seeded into the
+ * loader's intern table under their ids, so a string the batches share is held once, and the session
+ * ends with the documents, in order, that one load of the concatenated input builds.  While the arena is
+ * resident in HBM (every earlier batch device-loaded with no host-built document, GG_RESIDENT_ARENA not 0,
+ * no host writer run yet) and the new batch has no host-built document either, the new columns are
+ * copied behind the resident ones on the device, whose blocks grow by doubling; otherwise they are
+ * appended to the host columns.  Earlier documents are not parsed again.  An append invalidates the
+ * last evaluation (evaluate again before a report); the stats below count what the call added.
  * A document outside the device subset (libyaml-only syntax, duplicate keys, nesting past 64, a float
  * beyond the exact fast path, a raw character libyaml reads specially) is built by the host loader
  * and spliced in at its position.  A JSON document of GG_JSON_COOP_MIN bytes or more (default 65536; 0:
@@ -318,7 +326,7 @@ int32_t gg_session_add_synthetic(gg_session *s, uint64_t first, size_t n, int32_
  * GG_YAML_COOP unset or 1 (0: off) a block-style YAML document of that size is cut into segments by a
  * workgroup and parsed a lane per segment, the same threshold for both formats (GG_YAML_DEVICE=0 turns
  * every YAML path off);
- * gg_session_stat(s, 24) counts the documents the last load parsed that way.  Returns 0 when loaded, 1 when the batch is refused as a whole
+ * gg_session_stat(s, 24) counts the documents the session's device loads parsed that way.  Returns 0 when loaded, 1 when the batch is refused as a whole
  * (a batch-wide limit, or a refused document the host loader rejects too: nothing loaded, err->message
  * says why; gg_session_add_docs reports the loader error), -1 on error.  stats (may be NULL, 10 doubles):
  * kernel ms, nodes, distinct strings, pool bytes, text bytes, H2D ms, D2H ms, intern-table doublings,
@@ -329,7 +337,8 @@ int32_t gg_session_add_synthetic(gg_session *s, uint64_t first, size_t n, int32_
  * host into the documents the host loader builds: the session ends with the documents gg_session_add_docs
  * builds.  kernel ms then includes the merge kernel.  A merge that fails (a root key the parameters hold
  * too, root kinds that differ) is the first failing document's in document order: -1 with the
- * reference's panic message, and the session stays empty. */
+ * reference's panic message, and the session stays as it was before the call (as it does when 1 is
+ * returned). */
 int32_t gg_session_add_docs_device(gg_session *s, const char *const *texts, const size_t *lens, const char *const *names,
                                    size_t n, double *stats, extern_err_t *err);
 int32_t gg_session_add_synthetic_device(gg_session *s, uint64_t first, size_t n, int32_t n_resources, int32_t nthreads,
