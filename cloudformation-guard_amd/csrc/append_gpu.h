@@ -47,4 +47,36 @@ struct SeedTable {
 // aligned, strings zero padded to 16 bytes) under id off[i].  Null stream, not waited for.
 void append_seed_table(const SeedTable& T, const uint8_t* pool, const uint32_t* off, const uint32_t* len, uint32_t n);
 
+// ---- the intern state a session keeps in HBM between device loads ------------------------------------
+// The table a load leaves (keys, lengths, ids; the owners are that load's document indices and mean
+// nothing to the next one) and the pool with its cursor.  The next load carries the table into its working
+// table instead of seeding it from the host, and only the strings it adds come back to the host.  Blocks
+// from dev_alloc; the pool block holds pool_cap + 16 bytes, zero past pool_used only once a load has
+// cleared it.
+struct InternResident {
+  unsigned long long* tkey = nullptr;
+  uint32_t* tlen = nullptr;
+  uint32_t* tid = nullptr;
+  uint64_t slots = 0;          // a power of two, at least 2^16; 0: no state
+  uint8_t* pool = nullptr;
+  uint64_t pool_cap = 0;
+  uint64_t pool_used = 0;      // the cursor: equals the host pool's size while the state is valid
+  uint64_t fp_mask = 0;        // the keys were derived under this mask
+  uint64_t strings = 0;        // occupied slots (sizes the next working table)
+  uint64_t host_strings = 0;   // the host index's string count when the state was left
+};
+
+// Builds the working table `to` from the resident one: every occupied slot keeps its key, length and id and
+// becomes a seeded slot (kSeededOwner).  The same size: a straight copy of the slots.  A larger `to` (its
+// keys zeroed by the caller): every occupied slot is inserted with intern_slot's probe sequence -- the
+// probe start is a function of the stored key, so no pool byte is read; a probe run that finds no slot
+// stores to.bad_table in *to.bad.  Null stream, not waited for.
+void intern_carry(const InternResident& from, const SeedTable& to);
+
+// The occupied slots of T whose id is at or behind `threshold` (the pool size before the load: the strings
+// the load added), densely as (off[i], len[i]) pairs; *count (device, zeroed here) receives their number.
+// At most `cap` pairs are written, the count is the true one.  Table order inside a workgroup's 1024 slots,
+// workgroups in the order they finish.  Null stream, not waited for.
+void intern_compact(const SeedTable& T, uint32_t threshold, uint32_t* off, uint32_t* len, uint32_t* count, uint32_t cap);
+
 }  // namespace gg

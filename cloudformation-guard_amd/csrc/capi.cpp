@@ -439,6 +439,12 @@ struct gg_session {
   // nodes the resident blocks (dev_nodes, resident.*) have room for once a device append has grown them
   // (0: exactly resident.nodes); they grow by doubling, so appends copy each resident node O(1) times
   size_t arena_cap = 0;
+  // the device loader's interning state, kept in HBM from one device load to the next (append_gpu.h
+  // InternResident: fingerprint table, string pool, cursor) unless GG_RESIDENT_ARENA=0.  Valid for the next
+  // load while docs' pool and index are what that load left (intern_valid): a string interned on the host
+  // makes the pool longer, and the next device load seeds its table the old way and leaves a fresh state.
+  InternResident intern;
+  uint64_t seeded_strings = 0, index_strings = 0;   // the last device load (GpuLoadStats)
   // what the buffer set (dv) holds of this session's documents since the last upload: packed nodes, pool
   // bytes, and the resource map / type column of packed_docs documents built with these two key ids.
   // Documents are only appended (DocBatch), so the next upload packs and derives what follows and keeps
@@ -501,6 +507,7 @@ struct gg_session {
     release_bufs(dv);
     dev_free(dev_nodes);
     for (uint32_t* p : {resident.line, resident.col, resident.kline, resident.kcol}) dev_free(p);
+    intern_resident_free(intern);
   }
 };
 
@@ -4274,9 +4281,23 @@ static const auto make_room = [](auto& v, size_t extra) {   // amortised: append
   if (v.capacity() < v.size() + extra) v.reserve(std::max(v.size() + extra, 2 * v.capacity()));
 };
 
-static void append_doc_index(DocBatch& D, DocBatch& b, uint64_t first_node) {   // room made: nothing here throws
-  D.bytes = std::move(b.bytes);
-  D.islots = std::move(b.islots); D.ilen = std::move(b.ilen); D.iused = b.iused;
+// a load that carried the session's intern table (ic.in_place) hands over the added bytes and strings
+// only: the session's own pool and index are extended where they are, with nothing of theirs copied
+static void make_index_room(DocBatch& D, const DocBatch& b, const InternCarry& ic) {
+  make_room(D.base, b.ndocs()); make_room(D.roots, b.ndocs()); make_room(D.names, b.ndocs());
+  if (!ic.in_place) return;
+  make_room(D.bytes, b.bytes.size());
+  D.index_reserve(ic.add_off.size());
+}
+
+static void append_doc_index(DocBatch& D, DocBatch& b, uint64_t first_node, const InternCarry& ic) {   // room made: nothing here throws
+  if (ic.in_place) {
+    D.bytes.append(b.bytes);
+    D.adopt_bulk(ic.add_off.data(), ic.add_len.data(), ic.add_off.size(), (unsigned)report_threads());
+  } else {
+    D.bytes = std::move(b.bytes);
+    D.islots = std::move(b.islots); D.ilen = std::move(b.ilen); D.iused = b.iused;
+  }
   for (size_t k = 0; k < b.ndocs(); k++) {
     D.base.push_back(first_node + b.base[k]);
     D.roots.push_back(b.roots[k]);
@@ -4286,7 +4307,7 @@ static void append_doc_index(DocBatch& D, DocBatch& b, uint64_t first_node) {   
 
 // the arena is on the host (GG_RESIDENT_ARENA=0, a host writer ran, host-built documents are present, or
 // the new batch has some): the batch's columns, brought down by the loader, go behind the host columns
-static void append_host(gg_session* s, DocBatch& b) {
+static void append_host(gg_session* s, DocBatch& b, const InternCarry& ic) {
   DocBatch& D = s->docs;
   const size_t oldN = arena_nodes(s), addN = b.nodes.size();
   if (oldN + addN >= 0xFFFFFFFFull) throw std::runtime_error("batch too large for one session: split it (>= 2^32 arena nodes)");
@@ -4294,7 +4315,7 @@ static void append_host(gg_session* s, DocBatch& b) {
   // into this room): an allocation that fails leaves the arena where it was
   auto room = [&](auto& v) { if (v.capacity() < oldN + addN) v.reserve(std::max(oldN + addN, 2 * v.capacity())); };
   room(D.nodes); room(D.line); room(D.col); room(D.kline); room(D.kcol);
-  make_room(D.base, b.ndocs()); make_room(D.roots, b.ndocs()); make_room(D.names, b.ndocs());
+  make_index_room(D, b, ic);
   ensure_host_arena(s);
   D.nodes.resize(oldN + addN); D.line.resize(oldN + addN); D.col.resize(oldN + addN); D.kline.resize(oldN + addN); D.kcol.resize(oldN + addN);
   if (addN) {
@@ -4304,18 +4325,18 @@ static void append_host(gg_session* s, DocBatch& b) {
     memcpy(D.kline.data() + oldN, b.kline.data(), addN * 4);
     memcpy(D.kcol.data() + oldN, b.kcol.data(), addN * 4);
   }
-  append_doc_index(D, b, oldN);
+  append_doc_index(D, b, oldN, ic);
 }
 
 // the arena is resident and so is the new batch: its columns are copied behind the resident ones device
 // to device.  The resident blocks grow by doubling: new blocks from the block cache, the resident nodes
 // copied device to device, and the old blocks handed back once the device has drained.
-static void append_resident(gg_session* s, DocBatch& b, DNode* add_nodes, const ResidentArena& add) {
+static void append_resident(gg_session* s, DocBatch& b, DNode* add_nodes, const ResidentArena& add, const InternCarry& ic) {
   bind_device(s);
   DocBatch& D = s->docs;
   const uint64_t oldN = s->resident.nodes, addN = add.nodes, need = oldN + addN;
   if (need >= 0xFFFFFFFFull) throw std::runtime_error("batch too large for one session: split it (>= 2^32 arena nodes)");
-  make_room(D.base, b.ndocs()); make_room(D.roots, b.ndocs()); make_room(D.names, b.ndocs());
+  make_index_room(D, b, ic);
   struct Cols { DNode* nodes = nullptr; uint32_t* m[4] = {nullptr, nullptr, nullptr, nullptr}; };
   Cols cur, src;
   cur.nodes = (DNode*)s->dev_nodes; src.nodes = add_nodes;
@@ -4353,7 +4374,7 @@ static void append_resident(gg_session* s, DocBatch& b, DNode* add_nodes, const 
   s->arena_cap = cap;
   s->resident.nodes = need;
   s->dev_nodes_n = (size_t)need;
-  append_doc_index(D, b, oldN);
+  append_doc_index(D, b, oldN, ic);
 }
 
 // gg_session_add_docs_device with the input parameters given (a shard's or a chunk's session shares one
@@ -4406,8 +4427,16 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
     pm.params = params;
     // an appended batch stays resident only beside a resident arena
     const bool want_res = keep && (!appending || s->resident.nodes);
+    // the interning state the last device load left in HBM, while the session's pool and index are still
+    // the ones it was left for (a string interned on the host since then makes the pool longer)
+    if (s->intern.slots && !(keep && appending && s->intern.pool_used == s->docs.bytes.size() && s->intern.host_strings == s->docs.iused))
+      intern_resident_free(s->intern);
+    InternCarry ic;
+    ic.from = s->intern.slots ? &s->intern : nullptr;
+    // the state this load leaves is the session's only once the batch is (below); dropped on every other way out
+    struct InternHolder { InternCarry& c; gg_session* s; ~InternHolder() { if (c.next.slots) intern_resident_free(c.next, &s->intern); } } ihold{ic, s};
     if (!gpu_load_json(b, texts, lens, nm, n, st, why, &refused, &dev_nodes, want_res ? &res : nullptr, &pm,
-                       appending ? &s->docs : nullptr)) { set_note(err, why); return 1; }
+                       appending ? &s->docs : nullptr, keep ? &ic : nullptr)) { set_note(err, why); return 1; }
     struct ResHolder { ResidentArena& r; ~ResHolder() { for (uint32_t* p : {r.line, r.col, r.kline, r.kcol}) dev_free(p); } } rhold{res};
     if (getenv("GG_LOAD_TRACE"))
       fprintf(stderr, "[load] gpu_load_json returned %8.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl).count());
@@ -4452,8 +4481,8 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
       return -1;
     }
     if (appending) {
-      if (res.nodes && s->resident.nodes) append_resident(s, b, (DNode*)dev_nodes, res);
-      else append_host(s, b);   // the batch's own device copies go back to the cache (hold, rhold)
+      if (res.nodes && s->resident.nodes) append_resident(s, b, (DNode*)dev_nodes, res, ic);
+      else append_host(s, b, ic);   // the batch's own device copies go back to the cache (hold, rhold)
       s->uploaded = false;
       s->evaluated = false;   // the tiles are the earlier documents' only
       s->coop_docs += st.coop_docs;
@@ -4469,6 +4498,17 @@ static int32_t add_docs_device(gg_session* s, const DocBatch* params, const char
       res = ResidentArena{};
       s->coop_docs = st.coop_docs;
     }
+    // the batch is the session's: so is the interning state it left, if the session's pool is the device's
+    // (the host loader's documents and the parameters' strings are in the host pool only)
+    if (ic.next.slots && ic.next.pool_used == s->docs.bytes.size() && ic.next.host_strings == s->docs.iused) {
+      intern_resident_free(s->intern, &ic.next);
+      s->intern = ic.next;
+      ic.next = InternResident{};
+    } else if (s->intern.slots) {
+      if (ic.next.slots) intern_resident_free(ic.next, &s->intern);
+      intern_resident_free(s->intern);   // (it no longer describes the session's pool)
+    }
+    s->seeded_strings = st.seeded_strings; s->index_strings = st.index_strings;
     load_stats(st, stats);
     if (getenv("GG_LOAD_TRACE"))
       fprintf(stderr, "[load] session holds the batch %8.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl).count());
@@ -4707,6 +4747,8 @@ int64_t gg_session_stat(gg_session* s, int32_t what) {
     case 22: return (int64_t)s->lane_group;   // lanes per document of the lane kernel (1: one lane per tile)
     case 23: return (int64_t)s->lane_docs;    // documents per lane batch
     case 24: return (int64_t)s->coop_docs;    // documents the last device load parsed a workgroup each
+    case 25: return (int64_t)s->seeded_strings;   // strings the last device load's seeding kernel inserted (0: table carried in HBM)
+    case 26: return (int64_t)s->index_strings;    // strings the host index adopted in the last device load
     default: return -1;
   }
 }

@@ -716,20 +716,25 @@ void DocBatch::adopt(uint32_t off, uint32_t n) {
   islots[h] = off + 1; ilen[h] = n; iused++;
 }
 
-void DocBatch::adopt_bulk(const uint32_t* off, const uint32_t* len, size_t n, unsigned threads) {
-  if (!n) return;
+void DocBatch::index_reserve(size_t n) {
   size_t cap = islots.empty() ? 4096 : islots.size();
   while ((iused + n) * 2 > cap) cap *= 2;
-  if (cap != islots.size()) {
-    // rehash what is there (normally nothing: the device loader fills an empty batch)
-    const size_t keep = iused;
-    std::vector<uint32_t> old_s, old_l;
-    old_s.swap(islots); old_l.swap(ilen);
-    islots.assign(cap, 0); ilen.assign(cap, 0);
-    iused = 0;
-    for (size_t i = 0; i < old_s.size(); i++) if (old_s[i]) adopt(old_s[i] - 1, old_l[i]);
-    (void)keep;
+  if (cap == islots.size()) return;
+  // rehash what is there: nothing when the device loader fills an empty batch; a session's index that
+  // device appends extend doubles, so a string is rehashed O(1) times over any number of appends
+  std::vector<uint32_t> ns(cap, 0), nl(cap, 0);
+  for (size_t i = 0; i < islots.size(); i++) {
+    if (!islots[i]) continue;
+    size_t h = fnv1a(bytes.data() + islots[i] - 1, ilen[i]) & (cap - 1);
+    while (ns[h]) h = (h + 1) & (cap - 1);
+    ns[h] = islots[i]; nl[h] = ilen[i];
   }
+  islots.swap(ns); ilen.swap(nl);
+}
+
+void DocBatch::adopt_bulk(const uint32_t* off, const uint32_t* len, size_t n, unsigned threads) {
+  if (!n) return;
+  index_reserve(n);
   const size_t mask = islots.size() - 1;
   uint32_t* S = islots.data();
   uint32_t* L = ilen.data();

@@ -91,6 +91,8 @@ struct DocBatch {
   // concurrent linear-probing inserts (compare-and-swap on the slot; no deletions, so every string sits
   // at the first free slot from its hash at its insertion and find() reaches it)
   void adopt_bulk(const uint32_t* off, const uint32_t* len, size_t n, unsigned threads);
+  // room in the index for n more strings (what adopt_bulk does first: after it, adopt_bulk(n) allocates nothing)
+  void index_reserve(size_t n);
 
   // resizes every per-node column to s nodes, zero-filling new nodes (the columns default-initialise;
   // loaders that do not write every field of a new node use this)

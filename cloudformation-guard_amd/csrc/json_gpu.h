@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "append_gpu.h"
 #include "doc_loader.h"
 
 namespace gg {
@@ -21,6 +22,8 @@ struct GpuLoadStats {
   uint32_t table_retries = 0;   // intern-table doublings
   uint64_t refused_docs = 0;    // documents outside the device subset, built by the host loader
   uint64_t coop_docs = 0;       // documents the cooperative kernels parsed (a workgroup per document)
+  uint64_t seeded_strings = 0;  // strings the seeding kernel inserted (0: the resident table was carried, or nothing to seed)
+  uint64_t index_strings = 0;   // strings the load added, the ones the host index adopts
 };
 
 // Routing: a document of at least `coop_min` bytes is parsed cooperatively instead of by one lane: one that
@@ -69,6 +72,28 @@ struct ResidentArena {
 // two share keeps its id, new strings follow, and out's index covers both.  st.distinct_strings and
 // st.pool_bytes count what the load added.  out's nodes, bases and roots are its own documents' only: the
 // caller puts them behind append_to's.
+//
+// With `intern` as well the loader's interning state stays in HBM across loads (append_gpu.h InternResident).
+// intern->from, the state the last load left for append_to (the caller checks that append_to's pool and
+// index are still the ones it was left for), replaces the seeding: the working table is carried from it on
+// the device (intern_carry) before every run of the emit pass, the working pool is its block when that has
+// room and a larger block with the old bytes copied device to device otherwise, and nothing of append_to's
+// strings is listed, sorted or sent.  The passes never write into from's table, nor below its pool's
+// cursor.  intern->next receives the state after this load (slots 0: none -- a document was refused to the
+// host or the parameter merge added strings on the host, so the device no longer holds every string);
+// next.pool may be from->pool.  The caller owns next: it commits it with the batch or frees it
+// (intern_resident_free).  With intern->in_place set on return, out.bytes holds only the bytes the load added
+// (pool offsets from append_to's size on) and out's index is empty: add_off / add_len list the added
+// strings and the caller extends append_to's own pool and index with them.
+struct InternCarry {
+  const InternResident* from = nullptr;
+  InternResident next;
+  bool in_place = false;
+  std::vector<uint32_t> add_off, add_len;
+};
+// hands r's blocks back to the block cache (dev_free); a pool block it shares with `sharing` stays
+void intern_resident_free(InternResident& r, const InternResident* sharing = nullptr);
+
 struct ParamMerge {
   const DocBatch* params = nullptr;
   uint32_t fail_doc = NONE;
@@ -77,6 +102,6 @@ struct ParamMerge {
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused = nullptr,
                    void** keep_nodes = nullptr, ResidentArena* resident = nullptr, ParamMerge* merge = nullptr,
-                   const DocBatch* append_to = nullptr);
+                   const DocBatch* append_to = nullptr, InternCarry* intern = nullptr);
 
 }  // namespace gg

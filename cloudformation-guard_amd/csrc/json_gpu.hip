@@ -899,7 +899,8 @@ bool gpu_json_coop_doc(const char* text, size_t len, uint64_t coop_min, bool yam
 
 bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, const std::vector<std::string>& names,
                    size_t n, GpuLoadStats& st, std::string& why, std::vector<uint32_t>* refused,
-                   void** keep_nodes, ResidentArena* resident, ParamMerge* merge, const DocBatch* append_to) {
+                   void** keep_nodes, ResidentArena* resident, ParamMerge* merge, const DocBatch* append_to, InternCarry* intern) {
+  if (intern) { intern->next = InternResident{}; intern->in_place = false; intern->add_off.clear(); intern->add_len.clear(); }
   if (merge && !merge->params) merge = nullptr;
   if (merge) merge->fail_doc = NONE;
   if (resident) *resident = ResidentArena{};
@@ -924,7 +925,18 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   // neighbouring pool slots), and its pool as the new pool's first bytes
   std::vector<uint32_t> seed_off, seed_len;
   const uint64_t seed_bytes = append_to ? append_to->bytes.size() : 0;
-  if (append_to) {
+  uint64_t fp_mask = ~0ull;
+  if (const char* e = getenv("GG_JSON_FP_MASK")) {
+    // tests only: narrowed fingerprints collide, and every colliding document falls back to the host
+    fp_mask = strtoull(e, nullptr, 0);
+    static bool warned = false;
+    if (!warned) { warned = true; fprintf(stderr, "cfn-guard-mi355x: GG_JSON_FP_MASK=%s narrows the device loader's string fingerprints (test setting)\n", e); }
+  }
+  // the state the session's last load left in HBM stands in for all of that (append_gpu.h InternResident):
+  // its keys must be this load's keys and its pool the session's pool
+  const InternResident* from = intern && append_to ? intern->from : nullptr;
+  if (from && (!from->slots || from->fp_mask != fp_mask || from->pool_used != seed_bytes)) from = nullptr;
+  if (append_to && !from) {
     std::vector<uint64_t> sl;
     sl.reserve(append_to->iused);
     for (size_t k = 0; k < append_to->islots.size(); k++)
@@ -983,13 +995,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   const bool yaml_on = !getenv("GG_YAML_DEVICE") || atoi(getenv("GG_YAML_DEVICE")) != 0;
   JArgs A{};
   A.text = d_text.p; A.off = d_off.p; A.ndocs = (uint32_t)n;
-  A.fp_mask = ~0ull;
-  if (const char* e = getenv("GG_JSON_FP_MASK")) {
-    // tests only: narrowed fingerprints collide, and every colliding document falls back to the host
-    A.fp_mask = strtoull(e, nullptr, 0);
-    static bool warned = false;
-    if (!warned) { warned = true; fprintf(stderr, "cfn-guard-mi355x: GG_JSON_FP_MASK=%s narrows the device loader's string fingerprints (test setting)\n", e); }
-  }
+  A.fp_mask = fp_mask;
   A.n_nodes = d_nn.p; A.n_cont = d_nc.p; A.n_str = d_ns.p; A.bad = d_bad.p; A.doc_bad = d_doc_bad.p; A.is_yaml = d_yaml.p; A.bad_at = diag ? d_bad_at.p : nullptr;
   DevArr<uint16_t> d_counts; d_counts.alloc(total / 2 + 1);
   A.counts = d_counts.p;
@@ -1165,8 +1171,10 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   uint32_t start_log = 23;
   if (const char* e = getenv("GG_JSON_TABLE_LOG")) start_log = (uint32_t)std::max(16, std::min(28, atoi(e)));   // tests
   uint64_t tslots = 1ull << 16;
-  const uint64_t S_all = S + nseed;   // the seeded strings take a slot each
+  const uint64_t nold = from ? from->strings : nseed;
+  const uint64_t S_all = S + nold;   // the session's strings take a slot each
   while (tslots < 2 * S_all && tslots < (1ull << start_log)) tslots <<= 1;
+  if (from) tslots = std::max(tslots, from->slots);   // carried slot for slot, or rehashed into a larger table
   DevArr<unsigned long long> d_tkey, d_towner, d_pool_cursor;
   DevArr<uint32_t> d_tlen, d_tid;
   d_pool_cursor.alloc(1);
@@ -1174,6 +1182,13 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   // up to the bound every distinct string fits in (its bytes + 16 of alignment padding)
   const uint64_t pool_max = std::min<uint64_t>(seed_bytes + total + 16 * S + 16, 0xF0000000ull);
   uint64_t pool_cap = std::min<uint64_t>(seed_bytes + std::max<uint64_t>(total / 4, 1ull << 20), pool_max);
+  // the resident pool is the working pool when it has room (new strings only go behind its cursor, and a
+  // run that fails leaves nothing below it changed).  Room is a sixteenth of the text here, not the quarter a
+  // fresh block gets -- cfg2 templates add 0.6 % of their text -- so the block a first load left serves
+  // several appends of its size; a pool that fills after all runs again in a block of its own (BAD_POOL).
+  // Otherwise a fresh block sized as ever, the old bytes copied device to device.
+  bool pool_in_place = from && from->pool_cap >= std::min<uint64_t>(seed_bytes + std::max<uint64_t>(total / 16, 64ull << 10), pool_max);
+  if (pool_in_place) pool_cap = from->pool_cap;
   DevArr<uint8_t> d_pool, d_seed_pool;
   DevArr<uint32_t> d_seed_off, d_seed_len;
   if (nseed) {
@@ -1189,21 +1204,29 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   A.line = d_line.p; A.col = d_col.p; A.kline = d_kline.p; A.kcol = d_kcol.p;
   mark("device allocs");
   for (;;) {
-    if (d_pool.n != pool_cap + 16) d_pool.alloc(pool_cap + 16);
-    A.pool = d_pool.p; A.pool_cursor = d_pool_cursor.p; A.pool_cap = pool_cap;
+    A.pool_cursor = d_pool_cursor.p; A.pool_cap = pool_cap;
+    if (pool_in_place) {
+      A.pool = from->pool;
+      JCHK(hipMemset(A.pool + seed_bytes, 0, pool_cap + 16 - seed_bytes));   // what an earlier run or a failed load left there
+    } else {
+      if (d_pool.n != pool_cap + 16) d_pool.alloc(pool_cap + 16);
+      A.pool = d_pool.p;
+      JCHK(hipMemset(d_pool.p, 0, pool_cap + 16));
+      if (nseed) JCHK(hipMemcpy(d_pool.p, d_seed_pool.p, seed_bytes, hipMemcpyDeviceToDevice));
+      else if (from && seed_bytes) JCHK(hipMemcpy(d_pool.p, from->pool, seed_bytes, hipMemcpyDeviceToDevice));
+    }
     d_tkey.alloc(tslots); d_towner.alloc(tslots); d_tlen.alloc(tslots); d_tid.alloc(tslots);
-    JCHK(hipMemset(d_tkey.p, 0, tslots * 8));
+    if (!from || tslots != from->slots) JCHK(hipMemset(d_tkey.p, 0, tslots * 8));   // (the straight carry writes every slot)
     JCHK(hipMemcpy(d_pool_cursor.p, &seed_bytes, 8, hipMemcpyHostToDevice));
-    JCHK(hipMemset(d_pool.p, 0, pool_cap + 16));
-    if (nseed) JCHK(hipMemcpy(d_pool.p, d_seed_pool.p, seed_bytes, hipMemcpyDeviceToDevice));
     JCHK(hipMemcpy(d_doc_bad.p, d_doc_bad0.p, n * 4, hipMemcpyDeviceToDevice));
     A.tkey = d_tkey.p; A.tlen = d_tlen.p; A.towner = d_towner.p; A.tid = d_tid.p; A.tmask = tslots - 1;
 
-    // 2. emit, 3. own, 4. fix + verify; appending, the session's strings enter the table first
+    // 2. emit, 3. own, 4. fix + verify; appending, the session's strings enter the table first: carried
+    // from the table it keeps in HBM, or hashed again from its pool
     JCHK(hipEventRecord(e0));
-    if (nseed)
-      append_seed_table(SeedTable{A.tkey, A.tlen, A.towner, A.tid, A.tmask, A.fp_mask, A.bad, BAD_TABLE}, d_pool.p, d_seed_off.p,
-                        d_seed_len.p, (uint32_t)nseed);
+    const SeedTable working{A.tkey, A.tlen, A.towner, A.tid, A.tmask, A.fp_mask, A.bad, BAD_TABLE};
+    if (from) intern_carry(*from, working);
+    else if (nseed) append_seed_table(working, d_pool.p, d_seed_off.p, d_seed_len.p, (uint32_t)nseed);
     hipLaunchKernelGGL(json_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (yaml_on) hipLaunchKernelGGL(yaml_pass_kernel<M_EMIT>, dim3(dgrid), dim3(256), 0, 0, A);
     if (ncoop) hipLaunchKernelGGL(json_coop_emit_kernel, dim3(cgrid), dim3(256), 0, 0, A);
@@ -1228,6 +1251,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     }
     if (b == BAD_POOL && pool_cap < pool_max) {
       pool_cap = std::min<uint64_t>(pool_cap * 2, pool_max);
+      pool_in_place = false;   // a block of the working pool's own from here on
       JCHK(hipMemset(d_bad.p, 0, 4));
       st.table_retries++;
       continue;
@@ -1293,26 +1317,35 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
     }
   };
   uint64_t distinct = 0;
+  // with the table carried, no parameters to intern and no document for the host loader, the caller extends
+  // the session's own pool and index: out takes the added bytes and their list only (json_gpu.h InternCarry)
+  const bool in_place = from && !merge && !(refused && !refused->empty());
+  bool host_strings_added = false;
   auto fetch_pool_index = [&]() {
     // appending: the pool's first bytes are the session's own, and so is the start of the index
-    if (append_to) { out.bytes = append_to->bytes; out.islots = append_to->islots; out.ilen = append_to->ilen; out.iused = append_to->iused; }
-    out.bytes.resize(pool_used);
-    if (pool_used > seed_bytes) stg.d2h(&out.bytes[seed_bytes], d_pool.p + seed_bytes, pool_used - seed_bytes);
+    if (append_to && !in_place) { out.bytes = append_to->bytes; out.islots = append_to->islots; out.ilen = append_to->ilen; out.iused = append_to->iused; }
+    const uint64_t added = pool_used - seed_bytes, at = in_place ? 0 : seed_bytes;
+    out.bytes.resize(at + added);
+    if (added) stg.d2h(&out.bytes[at], A.pool + seed_bytes, added);
     mark("arena D2H");
-    std::vector<unsigned long long> tkey(tslots);
-    std::vector<uint32_t> tlen(tslots), tid(tslots);
-    JCHK(hipMemcpy(tkey.data(), d_tkey.p, tslots * 8, hipMemcpyDeviceToHost));
-    JCHK(hipMemcpy(tlen.data(), d_tlen.p, tslots * 4, hipMemcpyDeviceToHost));
-    JCHK(hipMemcpy(tid.data(), d_tid.p, tslots * 4, hipMemcpyDeviceToHost));
+    // the strings the load added, listed on the device (a seeded slot's id lies in the session's pool:
+    // indexed already); a string takes 16 pool bytes at least
+    const uint32_t cap = (uint32_t)(added / 16);
+    DevArr<uint32_t> d_aoff, d_alen, d_acount;
+    d_aoff.alloc(cap); d_alen.alloc(cap); d_acount.alloc(1);
+    intern_compact(SeedTable{A.tkey, A.tlen, A.towner, A.tid, A.tmask, A.fp_mask, A.bad, BAD_TABLE}, (uint32_t)seed_bytes, d_aoff.p,
+                   d_alen.p, d_acount.p, cap);
+    uint32_t nadd = 0;
+    JCHK(hipMemcpy(&nadd, d_acount.p, 4, hipMemcpyDeviceToHost));
+    if (nadd > cap) throw std::runtime_error("device loader: more added strings than the pool's added bytes hold");
+    std::vector<uint32_t> aoff(nadd), alen(nadd);
+    stg.d2h(aoff.data(), d_aoff.p, nadd * 4ull);
+    stg.d2h(alen.data(), d_alen.p, nadd * 4ull);
     st.d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    mark("table D2H");
-    std::vector<uint32_t> aoff, alen;
-    aoff.reserve(tslots / 2); alen.reserve(tslots / 2);
-    // (a seeded slot's id lies in the session's pool: indexed already)
-    for (uint64_t s = 0; s < tslots; s++) if (tkey[s] && tid[s] >= seed_bytes) { aoff.push_back(tid[s]); alen.push_back(tlen[s]); }
-    distinct = aoff.size();
-    mark("table scan");
-    out.adopt_bulk(aoff.data(), alen.data(), aoff.size(), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+    distinct = nadd;
+    mark("added strings D2H");
+    if (in_place) { intern->add_off.swap(aoff); intern->add_len.swap(alen); }
+    else out.adopt_bulk(aoff.data(), alen.data(), aoff.size(), std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
     mark("index built");
   };
   if (!merge) {
@@ -1330,6 +1363,7 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
       return false;
     }
     merge_template(out, *merge->params, tmpl);
+    host_strings_added = out.bytes.size() != pool_used;   // the parameters' strings: the device pool lacks them
     MergeArena MA{d_nodes.p, d_line.p, d_col.p, d_kline.p, d_kcol.p, d_nbase.p, d_nn.p, d_doc_bad.p, (uint32_t)n};
     MergeFail mf;
     const float mms = merge_params_device(MA, tmpl, mf);
@@ -1353,9 +1387,30 @@ bool gpu_load_json(DocBatch& out, const char* const* texts, const size_t* lens, 
   out.base.assign(nbase.begin(), nbase.begin() + n);
   out.names.assign(names.begin(), names.begin() + n);
   st.nodes = N; st.distinct_strings = distinct; st.pool_bytes = pool_used - seed_bytes;   // appending: what this load added
+  st.seeded_strings = nseed; st.index_strings = distinct;
   mark("adopt + names");
   if (keep_nodes) { *keep_nodes = d_nodes.p; d_nodes.p = nullptr; }
+  if (intern) {
+    intern->in_place = in_place;
+    // the table and the pool stay for the next load while they hold every string of the batch's pool
+    if (!host_strings_added && !(refused && !refused->empty())) {
+      InternResident& R = intern->next;
+      R.tkey = d_tkey.p; R.tlen = d_tlen.p; R.tid = d_tid.p; R.slots = tslots;
+      d_tkey.p = nullptr; d_tlen.p = nullptr; d_tid.p = nullptr;
+      R.pool = pool_in_place ? from->pool : d_pool.p;
+      if (!pool_in_place) d_pool.p = nullptr;
+      R.pool_cap = pool_cap; R.pool_used = pool_used; R.fp_mask = fp_mask;
+      R.strings = nold + distinct;
+      R.host_strings = in_place ? append_to->iused + distinct : out.iused;
+    }
+  }
   return true;
+}
+
+void intern_resident_free(InternResident& r, const InternResident* sharing) {
+  dev_free(r.tkey); dev_free(r.tlen); dev_free(r.tid);
+  if (!sharing || sharing->pool != r.pool) dev_free(r.pool);
+  r = InternResident{};
 }
 
 }  // namespace gg

@@ -849,7 +849,8 @@ class Session:
     STAT = {"ndocs": 0, "nfiles": 1, "nodes": 2, "bytes": 3, "fail": 4, "pass": 5, "skip": 6, "errors": 7,
             "records": 8, "arena_bytes": 9, "first_error": 10, "record_bytes": 11, "record_cap": 12,
             "max_top": 13, "slots": 14, "heap_bytes": 15, "retried": 16, "lane_slots": 17, "mode": 20,
-            "parse_errors": 21, "lane_group": 22, "lane_docs": 23, "coop_docs": 24}
+            "parse_errors": 21, "lane_group": 22, "lane_docs": 23, "coop_docs": 24,
+            "seeded_strings": 25, "index_strings": 26}
 
     def exit_code(self, output="json"):
         """the structured run's exit code over the evaluated documents, as the report would set it:
